@@ -10,6 +10,9 @@ rows), fp32-class arithmetic, alphas of configs/ours_cosine_no_preprocessing_ids
 SURVEY.md §6.  The 8192 rows of a step run as chunks of --chunk-rows rows (default 1024: 90 GB of activations per chunk plan),
 alternating over --streams engines on their own HIP streams so that one chunk's kernel tails overlap the other's.
 N>1: the same batch per rank (weak scaling, images are independent), one RCCL all-gather of accuracy counters.
+A plain run sets up, warms up, times --steps steps and prints the headline line (--dump-outputs DIR also writes what the last
+timed step computed); --full adds every other figure of the line (roofline, PMC traffic, per-kernel classes, secondary
+configurations, CPU baseline and oracle parity), several minutes more.
 """
 import argparse
 import json
@@ -693,6 +696,31 @@ def log(msg):
     print(f'[bench {time.strftime("%H:%M:%S")}] {msg}', file=sys.stderr, flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, step):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, as float32 .npy files under `d`, so that two
+    builds can be compared output for output on the same seeded inputs:
+      x_adv       the images after the step's PGD update           (images, 3, H, W)
+      logits      the EoT-mean logits the step computed             (images, classes)
+      input_grad  d CE / d image of the last chunk each engine ran, i.e. of the last len(engines) chunks' images, in image order
+    At most DUMP_LIMIT_BYTES in all: an array over its share keeps a fixed, seeded sample of its rows (same sample every run)."""
+    import numpy as np
+    n_eng, per = len(step.engines), step.per
+    n_chunks = step.x_orig.shape[0] // per
+    grads = [step.engines[c % n_eng].dx[:per] for c in range(n_chunks - n_eng, n_chunks)]
+    arrays = {'x_adv': step.x_adv, 'logits': step.logits, 'input_grad': torch.cat(grads)}
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share:
+            keep = share // a[0].nbytes
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(d, f'{name}.npy'), np.ascontiguousarray(a))
+
+
 class StubEngine:
     """TEST REHEARSAL ONLY (--stub-engine, gloo): a CPU stand-in with the engine's buffers so that the launcher, the
     rendezvous, the barrier + max-over-ranks timing, the all-gather and the JSON line can be exercised without a GPU.
@@ -741,6 +769,12 @@ def launch_ranks(args, argv):
     threads = [threading.Thread(target=drain, args=(i,)) for i in range(n)]
     for t in threads:
         t.start()
+    # a rank that fails leaves the others waiting for it in the rendezvous or a collective: stop them instead of waiting
+    while any(p.poll() is None for p in procs) and not any(p.poll() for p in procs):
+        time.sleep(0.1)
+    for p in procs:
+        if p.poll() is None:
+            p.terminate()
     codes = [p.wait() for p in procs]
     for t in threads:
         t.join()
@@ -797,9 +831,19 @@ def main():
                     help='skip every secondary measurement (rows256, shared encoder, fp32, reference protocol, e4e defender)')
     ap.add_argument('--stub-engine', action='store_true',
                     help='TEST REHEARSAL ONLY: CPU stand-in engines (needs --backend gloo); exercises launcher / collectives / JSON')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline (several minutes): PMC passes, roofline, per-kernel-class figures, '
+                         'BPDA, the 256-row and shared-encoder variants, the secondary measurements, the CPU baseline with its oracle '
+                         'parity and the robust-accuracy delta (the --no-* / --defender-* options above select among them).  Without it '
+                         'a run sets up, warms up, times --steps steps and prints the headline line')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed (rank 0) as float32 DIR/<name>.npy, at most '
+                         '64 MB in all (see dump_outputs)')
     args = ap.parse_args()
     if args.stub_engine and args.backend != 'gloo':
         raise SystemExit('--stub-engine is a CPU rehearsal of the multi-rank plumbing: use it with --backend gloo')
+    if args.steps < 1:
+        raise SystemExit('--steps must be at least 1: the result line reports the time of one timed step')
 
     if args.pmc_child:
         return pmc_child(args)
@@ -813,7 +857,7 @@ def main():
                          'itself; under torch.distributed.run pass the same N)')
     pmc_bytes, pmc_note = None, 'skipped'
     args.defender_pmc = {}
-    if rank == 0 and world == 1 and not args.no_pmc and not args.stub_engine:
+    if args.full and rank == 0 and world == 1 and not args.no_pmc and not args.stub_engine:
         log('PMC passes (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE over one chunk replay in a child process) ...')
         pmc_bytes, pmc_note = measure_pmc_traffic(args)           # before this process initialises the GPU
         log(f'PMC: {pmc_bytes} bytes per conv launch ({pmc_note[:80]})')
@@ -870,6 +914,9 @@ def main():
         streams = [torch.cuda.Stream(device=device) for _ in engines]
     log(f'engines ready: {sum(e.bytes for e in engines) / 1e9:.1f} GB activations + weights, {len(eng.fwd)} fwd + {len(eng.bwd)} bwd ops per chunk, '
         f'{n_chunks} chunks per step')
+    # the latent noise of every step comes from the default generators, whose seed otherwise changes from process to process:
+    # with a fixed seed two runs with the same arguments see the same inputs (--dump-outputs compares builds output for output)
+    torch.manual_seed(1234 + rank)
     g = torch.Generator(device=device).manual_seed(1234 + rank)      # every rank its own images (weak scaling)
     x = torch.rand(args.images, 3, 64, 64, device=device, generator=g)
     # labels = clean prediction of the defender, so that the attack starts from "correct" 
@@ -911,6 +958,9 @@ def main():
     if rank == 0 and int(round(float(counters[1].item()))) != args.images * world:
         # every rank contributes its image count to the gathered counters: anything else means a rank's result went missing
         raise SystemExit(f'accuracy counters cover {float(counters[1].item()):.0f} images, expected {args.images} x {world} ranks')
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, step)
+        log(f'outputs of the last timed step written to {args.dump_outputs}')
     if rank == 0 and args.stub_engine:
         print(json.dumps({'metric': 'purified images/sec (attack+encode+decode)', 'value': rows_per_step * world * args.steps / dt,
                           'unit': 'defender rows/s (rows = images x EoT-32)', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -921,19 +971,6 @@ def main():
     elif rank == 0:
         log(f'timed region: {dt:.3f} s for {args.steps} steps')
         rows_total = rows_per_step * world * args.steps
-        # ---- roofline of the dominant kernel (conv_mfma_kernel): HIP events on the plan's stream, per launch
-        s = eng.stream()
-        f_ms, fc_ms, fn = eng.fwd.time(s, iters=1, per_conv=True)
-        b_ms, bc_ms, bn = eng.bwd.time(s, iters=1, per_conv=True)
-        flops = conv_algorithmic_flops(eng.fwd) + conv_algorithmic_flops(eng.bwd)
-        conv_s = (fc_ms + bc_ms) / 1e3
-        achieved = flops / conv_s / 1e12
-        peak = PEAK_BF16X3_TFLOPS if args.precision == 'bf16x3' else PEAK_FP32_MFMA_TFLOPS
-        try:
-            mp = measured_peaks(device)
-        except Exception as ex:
-            mp = {'hbm_copy_tbps': None, 'bf16_mfma_tflops': None, 'how': f'failed: {ex}'}
-        meas_ceiling = mp['bf16_mfma_tflops'] / 3.0 if (mp['bf16_mfma_tflops'] and args.precision == 'bf16x3') else None
         out = {
             'metric': 'purified images/sec (attack+encode+decode)',
             'value': rows_total / dt,
@@ -951,171 +988,186 @@ def main():
                        'encoder_shared_by_eot_replicas': bool(eng.share_encoder), 'images_per_step': args.images * world,
                        'images_per_s': args.images * world * args.steps / dt,
                        'parallelism': f'image-sharded x{world}'},
-            'roofline': {'bound': 'mfma',
-                         'kernel': 'ga::conv_bf3_kernel + ga::conv_halo3_kernel + ga::conv_thin3_kernel + ga::conv_mfma_kernel (implicit-GEMM conv, all instantiations)',
-                         'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s', 'frac': achieved / peak, 'traffic': pmc_bytes,
-                         'measured_peak': dict(mp, bf16x3_ceiling_tflops=meas_ceiling),
-                         'frac_of_measured_peak': (achieved / meas_ceiling) if meas_ceiling else None,
-                         'traffic_note': 'HBM bytes per conv launch: ' + pmc_note + '; algorithmic bytes per launch beside it',
-                         'algorithmic_bytes_per_launch': (conv_algorithmic_bytes(eng.fwd) + conv_algorithmic_bytes(eng.bwd)) / (fn + bn),
-                         'peak_note': ('dense bf16 MFMA peak 2500 TFLOP/s / 3 MFMAs per fp32-class product; achieved counts '
-                                       'algorithmic (1x) flops' if args.precision == 'bf16x3' else 'fp32 MFMA peak'),
-                         'achieved_over_fp32_mfma_peak': achieved / PEAK_FP32_MFMA_TFLOPS,
-                         'launches_per_chunk': int(fn + bn), 'avg_launch_ms': (fc_ms + bc_ms) / (fn + bn),
-                         'algorithmic_gflop_per_chunk': flops / 1e9, 'chunks_per_step': n_chunks,
-                         'conv_ms_per_chunk': fc_ms + bc_ms, 'plan_ms_fwd': f_ms, 'plan_ms_bwd': b_ms,
-                         'note': 'per-launch durations: HIP events around every conv launch of one chunk (forward + backward '
-                                 'plan) on one stream, right after the timed region'},
             'accuracy_counters': [float(counters[0].item()), float(counters[1].item())],
         }
-        # the second kernel family of the path: the fused decoder cells (ga_dec_cell), per-op HIP events of one chunk
-        from gen_adversarial_amd import _lib as L
-        cell_ms, cell_n = 0.0, 0
-        headline_fused = sum(isinstance(dsc, (L.DecCellDesc, L.DecCellHaloDesc)) for plan in (eng.fwd, eng.bwd) for dsc in plan.descs)
-        for plan in (eng.fwd, eng.bwd):
-            for dsc, ms in zip(plan.descs, plan.profile(s)):
-                if isinstance(dsc, (L.DecCellDesc, L.DecCellHaloDesc)):
-                    cell_ms, cell_n = cell_ms + ms, cell_n + 1
-        if cell_n:
-            cfl = dec_cell_algorithmic_flops(eng.fwd) + dec_cell_algorithmic_flops(eng.bwd)
-            out['fused_decoder_cells'] = {
-                'kernel': 'ga::dec_cell_fwd_kernel + ga::dec_cell_bwd_kernel (1x1 expand -> SiLU -> depthwise 5x5 -> SiLU -> 1x1 project, '
-                          'one launch per direction; the 6C-wide tensors stay in LDS / registers)',
-                'launches_per_chunk': cell_n, 'ms_per_chunk': cell_ms, 'avg_launch_ms': cell_ms / cell_n,
-                'algorithmic_gflop_per_chunk': cfl / 1e9, 'achieved_tflops': cfl / (cell_ms / 1e3) / 1e12,
-                'bound': 'vector ALU + LDS of one wave per SIMD (two quarter-rate transcendentals per SiLU, 25 FMAs and 2.7 LDS reads per '
-                         'depthwise output); the contractions are 25 % of its clocks (tools/dec_cell_trace.py)',
-                'share_of_plan_ms': cell_ms / (f_ms + b_ms)}
-        try:
-            out['hbm_bound_kernel_classes'] = dict(
-                hbm_bound_classes(eng, s), _note='BASELINE.md §3: achieved_hbm = algorithmic bytes (inputs + outputs of the op, fp32) / '
-                f'HIP-event kernel time / 8 TB/s, per memory-bound kernel class of one {args.chunk_rows}-row chunk (forward + backward plan, one stream)')
-        except Exception as ex:
-            out['hbm_bound_kernel_classes'] = {'_note': f'failed: {type(ex).__name__}: {ex}'}
-        if world == 1 and not args.no_secondary and not args.stub_engine:
-            # BASELINE.json configs[3] names "PGD-40 + BPDA": the same 8192-row step with the purifier's Jacobian replaced by the
-            # identity in the backward pass (forward through purifier + classifier, backward through the classifier alone)
+        if args.full:
+            # ---- roofline of the dominant kernel (conv_mfma_kernel): HIP events on the plan's stream, per launch
+            s = eng.stream()
+            f_ms, fc_ms, fn = eng.fwd.time(s, iters=1, per_conv=True)
+            b_ms, bc_ms, bn = eng.bwd.time(s, iters=1, per_conv=True)
+            flops = conv_algorithmic_flops(eng.fwd) + conv_algorithmic_flops(eng.bwd)
+            conv_s = (fc_ms + bc_ms) / 1e3
+            achieved = flops / conv_s / 1e12
+            peak = PEAK_BF16X3_TFLOPS if args.precision == 'bf16x3' else PEAK_FP32_MFMA_TFLOPS
             try:
-                st_b = AttackStep(engines, streams, labels, x, bpda=True)
-                tb = _time_steps(st_b, 3, warm=1)
-                out.setdefault('secondary', {})['pgd_bpda'] = {
-                    'rows_per_s': rows_per_step / tb, 'ms_per_step': tb * 1e3,
-                    'what': f'--attack pgd-bpda at the headline configuration: {args.images} images x EoT {args.eot} per step, full forward, '
-                            'backward through the VGG classifier only (Engine.backward(identity_purifier=True))'}
-                del st_b
+                mp = measured_peaks(device)
             except Exception as ex:
-                out.setdefault('secondary', {})['pgd_bpda'] = {'rows_per_s': None, 'what': f'failed: {ex}'}
-        if world == 1 and rows_per_step != 256 and not args.no_rows256:
-            # SURVEY.md §8(d) words configs[1] as R = 256 defender rows (8 images x EoT 32) in ONE plan run: the same
-            # attack step at that size, one engine, one stream, reported beside the headline (never as `value`)
+                mp = {'hbm_copy_tbps': None, 'bf16_mfma_tflops': None, 'how': f'failed: {ex}'}
+            meas_ceiling = mp['bf16_mfma_tflops'] / 3.0 if (mp['bf16_mfma_tflops'] and args.precision == 'bf16x3') else None
+            out['roofline'] = {'bound': 'mfma',
+                               'kernel': 'ga::conv_bf3_kernel + ga::conv_halo3_kernel + ga::conv_thin3_kernel + ga::conv_mfma_kernel '
+                                         '(implicit-GEMM conv, all instantiations)',
+                               'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s', 'frac': achieved / peak, 'traffic': pmc_bytes,
+                               'measured_peak': dict(mp, bf16x3_ceiling_tflops=meas_ceiling),
+                               'frac_of_measured_peak': (achieved / meas_ceiling) if meas_ceiling else None,
+                               'traffic_note': 'HBM bytes per conv launch: ' + pmc_note + '; algorithmic bytes per launch beside it',
+                               'algorithmic_bytes_per_launch': (conv_algorithmic_bytes(eng.fwd) + conv_algorithmic_bytes(eng.bwd)) / (fn + bn),
+                               'peak_note': ('dense bf16 MFMA peak 2500 TFLOP/s / 3 MFMAs per fp32-class product; achieved counts '
+                                             'algorithmic (1x) flops' if args.precision == 'bf16x3' else 'fp32 MFMA peak'),
+                               'achieved_over_fp32_mfma_peak': achieved / PEAK_FP32_MFMA_TFLOPS,
+                               'launches_per_chunk': int(fn + bn), 'avg_launch_ms': (fc_ms + bc_ms) / (fn + bn),
+                               'algorithmic_gflop_per_chunk': flops / 1e9, 'chunks_per_step': n_chunks,
+                               'conv_ms_per_chunk': fc_ms + bc_ms, 'plan_ms_fwd': f_ms, 'plan_ms_bwd': b_ms,
+                               'note': 'per-launch durations: HIP events around every conv launch of one chunk (forward + backward '
+                                       'plan) on one stream, right after the timed region'}
+            # the second kernel family of the path: the fused decoder cells (ga_dec_cell), per-op HIP events of one chunk
+            from gen_adversarial_amd import _lib as L
+            cell_ms, cell_n = 0.0, 0
+            headline_fused = sum(isinstance(dsc, (L.DecCellDesc, L.DecCellHaloDesc)) for plan in (eng.fwd, eng.bwd) for dsc in plan.descs)
+            for plan in (eng.fwd, eng.bwd):
+                for dsc, ms in zip(plan.descs, plan.profile(s)):
+                    if isinstance(dsc, (L.DecCellDesc, L.DecCellHaloDesc)):
+                        cell_ms, cell_n = cell_ms + ms, cell_n + 1
+            if cell_n:
+                cfl = dec_cell_algorithmic_flops(eng.fwd) + dec_cell_algorithmic_flops(eng.bwd)
+                out['fused_decoder_cells'] = {
+                    'kernel': 'ga::dec_cell_fwd_kernel + ga::dec_cell_bwd_kernel (1x1 expand -> SiLU -> depthwise 5x5 -> SiLU -> 1x1 project, '
+                              'one launch per direction; the 6C-wide tensors stay in LDS / registers)',
+                    'launches_per_chunk': cell_n, 'ms_per_chunk': cell_ms, 'avg_launch_ms': cell_ms / cell_n,
+                    'algorithmic_gflop_per_chunk': cfl / 1e9, 'achieved_tflops': cfl / (cell_ms / 1e3) / 1e12,
+                    'bound': 'vector ALU + LDS of one wave per SIMD (two quarter-rate transcendentals per SiLU, 25 FMAs and 2.7 LDS reads per '
+                             'depthwise output); the contractions are 25 % of its clocks (tools/dec_cell_trace.py)',
+                    'share_of_plan_ms': cell_ms / (f_ms + b_ms)}
             try:
-                n8 = 256 // args.eot
-                eng8, _ = build_model(device, 256, args.eot, seed=0, precision=args.precision,
-                                      share_encoder=args.share_encoder, store=eng.store)
-                step8 = AttackStep([eng8], [torch.cuda.Stream(device=device)], labels[:n8].clone(), x[:n8].clone())
-                for _ in range(3):
-                    step8()
-                torch.cuda.synchronize()
-                t8 = time.perf_counter()
-                for _ in range(20):
-                    step8()
-                torch.cuda.synchronize()
-                t8 = (time.perf_counter() - t8) / 20
-                out['config']['rows256_single_plan'] = {'rows_per_s': 256 / t8, 'ms_per_step': t8 * 1e3,
-                                                        'what': f'{n8} images x EoT {args.eot} = 256 rows per step, 1 stream'}
-                del step8, eng8
+                out['hbm_bound_kernel_classes'] = dict(
+                    hbm_bound_classes(eng, s), _note='BASELINE.md §3: achieved_hbm = algorithmic bytes (inputs + outputs of the op, fp32) / '
+                    f'HIP-event kernel time / 8 TB/s, per memory-bound kernel class of one {args.chunk_rows}-row chunk (forward + backward plan, one stream)')
             except Exception as ex:
-                out['config']['rows256_single_plan'] = {'rows_per_s': None, 'what': f'failed: {ex}'}
-        store = eng.store
-        if world == 1 and not args.no_shared_variant and not eng.share_encoder and eng.noise_eps == 0.0 and args.eot > 1:
-            # the defender API's default (NVAEDefenseModel): with no input noise configured the encoder pass is the same for
-            # the EoT replicas of an image and runs once per image — identical numbers, fewer FLOPs.  Reported beside the
-            # headline (which runs the literal x.repeat(eot) path), never as `value`.
-            try:
-                n_chunk_s = min(n_chunks, 4)
+                out['hbm_bound_kernel_classes'] = {'_note': f'failed: {type(ex).__name__}: {ex}'}
+            if world == 1 and not args.no_secondary and not args.stub_engine:
+                # BASELINE.json configs[3] names "PGD-40 + BPDA": the same 8192-row step with the purifier's Jacobian replaced by the
+                # identity in the backward pass (forward through purifier + classifier, backward through the classifier alone)
+                try:
+                    st_b = AttackStep(engines, streams, labels, x, bpda=True)
+                    tb = _time_steps(st_b, 3, warm=1)
+                    out.setdefault('secondary', {})['pgd_bpda'] = {
+                        'rows_per_s': rows_per_step / tb, 'ms_per_step': tb * 1e3,
+                        'what': f'--attack pgd-bpda at the headline configuration: {args.images} images x EoT {args.eot} per step, full forward, '
+                                'backward through the VGG classifier only (Engine.backward(identity_purifier=True))'}
+                    del st_b
+                except Exception as ex:
+                    out.setdefault('secondary', {})['pgd_bpda'] = {'rows_per_s': None, 'what': f'failed: {ex}'}
+            if world == 1 and rows_per_step != 256 and not args.no_rows256:
+                # SURVEY.md §8(d) words configs[1] as R = 256 defender rows (8 images x EoT 32) in ONE plan run: the same
+                # attack step at that size, one engine, one stream, reported beside the headline (never as `value`)
+                try:
+                    n8 = 256 // args.eot
+                    eng8, _ = build_model(device, 256, args.eot, seed=0, precision=args.precision,
+                                          share_encoder=args.share_encoder, store=eng.store)
+                    step8 = AttackStep([eng8], [torch.cuda.Stream(device=device)], labels[:n8].clone(), x[:n8].clone())
+                    for _ in range(3):
+                        step8()
+                    torch.cuda.synchronize()
+                    t8 = time.perf_counter()
+                    for _ in range(20):
+                        step8()
+                    torch.cuda.synchronize()
+                    t8 = (time.perf_counter() - t8) / 20
+                    out['config']['rows256_single_plan'] = {'rows_per_s': 256 / t8, 'ms_per_step': t8 * 1e3,
+                                                            'what': f'{n8} images x EoT {args.eot} = 256 rows per step, 1 stream'}
+                    del step8, eng8
+                except Exception as ex:
+                    out['config']['rows256_single_plan'] = {'rows_per_s': None, 'what': f'failed: {ex}'}
+            store = eng.store
+            if world == 1 and not args.no_shared_variant and not eng.share_encoder and eng.noise_eps == 0.0 and args.eot > 1:
+                # the defender API's default (NVAEDefenseModel): with no input noise configured the encoder pass is the same for
+                # the EoT replicas of an image and runs once per image — identical numbers, fewer FLOPs.  Reported beside the
+                # headline (which runs the literal x.repeat(eot) path), never as `value`.
+                try:
+                    n_chunk_s = min(n_chunks, 4)
+                    step = None
+                    engines.clear()
+                    del eng
+                    free_gpu_memory()
+                    es = build_model(device, args.chunk_rows, args.eot, seed=0, precision=args.precision, share_encoder=True, store=store)[0]
+                    eng_s = [es] + [Engine_clone(es, model, device, args) for _ in range(n_eng - 1)]
+                    imgs = n_chunk_s * args.chunk_rows // args.eot
+                    st = AttackStep(eng_s, streams, labels[:imgs].clone(), x[:imgs].clone())
+                    st()
+                    torch.cuda.synchronize()
+                    ts = time.perf_counter()
+                    for _ in range(3):
+                        st()
+                    torch.cuda.synchronize()
+                    ts = (time.perf_counter() - ts) / 3
+                    out['config']['shared_encoder_variant'] = {
+                        'rows_per_s': n_chunk_s * args.chunk_rows / ts,
+                        'what': f'{imgs} images x EoT {args.eot} per step, encoder once per image (exact without input noise); API default'}
+                    del st, eng_s, es
+                    free_gpu_memory()
+                except Exception as ex:
+                    out['config']['shared_encoder_variant'] = {'rows_per_s': None, 'what': f'failed: {ex}'}
+            if world == 1 and not args.no_secondary:
+                # the headline engines are no longer needed: free their 134 GB before the other secondary measurements
                 step = None
                 engines.clear()
-                del eng
+                eng = None
                 free_gpu_memory()
-                es = build_model(device, args.chunk_rows, args.eot, seed=0, precision=args.precision, share_encoder=True, store=store)[0]
-                eng_s = [es] + [Engine_clone(es, model, device, args) for _ in range(n_eng - 1)]
-                imgs = n_chunk_s * args.chunk_rows // args.eot
-                st = AttackStep(eng_s, streams, labels[:imgs].clone(), x[:imgs].clone())
-                st()
-                torch.cuda.synchronize()
-                ts = time.perf_counter()
-                for _ in range(3):
-                    st()
-                torch.cuda.synchronize()
-                ts = (time.perf_counter() - ts) / 3
-                out['config']['shared_encoder_variant'] = {
-                    'rows_per_s': n_chunk_s * args.chunk_rows / ts,
-                    'what': f'{imgs} images x EoT {args.eot} per step, encoder once per image (exact without input noise); API default'}
-                del st, eng_s, es
-                free_gpu_memory()
-            except Exception as ex:
-                out['config']['shared_encoder_variant'] = {'rows_per_s': None, 'what': f'failed: {ex}'}
-        if world == 1 and not args.no_secondary:
-            # the headline engines are no longer needed: free their 134 GB before the other secondary measurements
-            step = None
-            engines.clear()
-            eng = None
-            free_gpu_memory()
-            secondary_measurements(out, args, device, model, store, x, labels)
-        if not args.no_cpu_baseline and world == 1:
-            try:
-                log('cpu baseline (oracle on host cores) ...')
-                def parity(xc, epsc, lc, gc):
-                    # the same 128 rows on the HIP path (oracle as the checker): logits and input gradient of the CE loss.  The
-                    # headline's chunk plans run 32 decoder cells per direction as fused ga_dec_cell launches; at 128 rows the
-                    # engine would pick the three unfused launches (fewer than 160 workgroups), so the gate is forced here: the
-                    # CHECKED path is the TIMED path (`fused_cells` says how many of the replay's launches were ga_dec_cell)
-                    from gen_adversarial_amd.engine import Engine
-                    from gen_adversarial_amd import _lib as L_
-                    gate = Engine.fuse_min_workgroups
-                    Engine.fuse_min_workgroups = 0
-                    try:
-                        e = build_model(device, xc.shape[0] * args.eot, args.eot, seed=0, precision=args.precision, store=store)[0]
-                    finally:
-                        Engine.fuse_min_workgroups = gate
-                    n_fused = sum(isinstance(d_, (L_.DecCellDesc, L_.DecCellHaloDesc)) for pl in (e.fwd, e.bwd) for d_ in pl.descs)
-                    e.x_in.copy_(xc.to(device))
-                    for b_, e_ in zip(e.eps, epsc):
-                        b_.copy_(e_.to(device))
-                    e.forward()
-                    lg = e.logits.view(-1, args.eot, e.logits.shape[-1]).mean(dim=1)
-                    p = torch.softmax(lg, dim=1)
-                    p[torch.arange(p.shape[0], device=p.device), lg.argmax(dim=1)] -= 1.0
-                    e.dlogits.view(-1, args.eot, p.shape[-1]).copy_((p / args.eot).unsqueeze(1).expand(-1, args.eot, -1))
-                    e.backward()
-                    ref_mean = lc.view(-1, args.eot, lc.shape[-1]).mean(dim=1)
-                    gd = (e.dx.cpu() - gc).double()
-                    out['parity_vs_oracle'] = {
-                        'rows': int(lc.shape[0]), 'max_abs_logit_err': float((e.logits.cpu() - lc).abs().max()),
-                        'argmax_agree': int((lg.argmax(dim=1).cpu() == ref_mean.argmax(dim=1)).sum()), 'images': int(ref_mean.shape[0]),
-                        'input_grad_rel_l2': float(gd.norm() / gc.double().norm()),
-                        'fused_cells': int(n_fused),
-                        'headline_fused_cells': int(headline_fused),
-                        'note': 'same inputs and latent noise as the cpu_baseline sample, replayed with the fused decoder cells forced '
-                                'on (the kernels the timed chunk plans select); tolerance of the path: 1e-3 on logits'}
-                out['cpu_baseline'] = cpu_baseline(model, 4 * args.eot, args.eot, check=parity)      # 128 rows: ~16 s of oracle time on 16 threads
-                log('cpu baseline done')
-                if args.robust_acc_images > 0:
-                    # robust accuracy under the reference's APGD-CE, HIP vs oracle, every draw pinned, with the paired 95 % interval of
-                    # the difference (the oracle as the checker, on a reduced model it can run hundreds of attacks on:
-                    # tests/robust_acc_attack.py; VERDICT r03 "next round" #3)
-                    log(f'robust accuracy under APGD-CE on {args.robust_acc_images} images (oracle on the host cores) ...')
-                    try:
-                        sys.path.insert(0, os.path.join(ROOT, 'tests'))
-                        from robust_acc_attack import robust_accuracy_under_attack
-                        free_gpu_memory()
-                        out['robust_accuracy_delta'] = robust_accuracy_under_attack(device, n_images=args.robust_acc_images, eot=2, n_iter=5,
-                                                                                    bound=2.0, chunk_images=min(64, args.robust_acc_images))
-                    except Exception as ex:
-                        out['robust_accuracy_delta'] = {'delta': None, 'what': f'failed: {type(ex).__name__}: {ex}'}
-                    log('robust-accuracy delta done')
-            except Exception as ex:   # the baseline is a reported number, never a reason to lose the bench line
-                out['cpu_baseline'] = {'value': None, 'unit': 'rows/s', 'cores': 0, 'kind': 'port', 'sample': f'failed: {ex}'}
+                secondary_measurements(out, args, device, model, store, x, labels)
+            if not args.no_cpu_baseline and world == 1:
+                try:
+                    log('cpu baseline (oracle on host cores) ...')
+                    def parity(xc, epsc, lc, gc):
+                        # the same 128 rows on the HIP path (oracle as the checker): logits and input gradient of the CE loss.  The
+                        # headline's chunk plans run 32 decoder cells per direction as fused ga_dec_cell launches; at 128 rows the
+                        # engine would pick the three unfused launches (fewer than 160 workgroups), so the gate is forced here: the
+                        # CHECKED path is the TIMED path (`fused_cells` says how many of the replay's launches were ga_dec_cell)
+                        from gen_adversarial_amd.engine import Engine
+                        from gen_adversarial_amd import _lib as L_
+                        gate = Engine.fuse_min_workgroups
+                        Engine.fuse_min_workgroups = 0
+                        try:
+                            e = build_model(device, xc.shape[0] * args.eot, args.eot, seed=0, precision=args.precision, store=store)[0]
+                        finally:
+                            Engine.fuse_min_workgroups = gate
+                        n_fused = sum(isinstance(d_, (L_.DecCellDesc, L_.DecCellHaloDesc)) for pl in (e.fwd, e.bwd) for d_ in pl.descs)
+                        e.x_in.copy_(xc.to(device))
+                        for b_, e_ in zip(e.eps, epsc):
+                            b_.copy_(e_.to(device))
+                        e.forward()
+                        lg = e.logits.view(-1, args.eot, e.logits.shape[-1]).mean(dim=1)
+                        p = torch.softmax(lg, dim=1)
+                        p[torch.arange(p.shape[0], device=p.device), lg.argmax(dim=1)] -= 1.0
+                        e.dlogits.view(-1, args.eot, p.shape[-1]).copy_((p / args.eot).unsqueeze(1).expand(-1, args.eot, -1))
+                        e.backward()
+                        ref_mean = lc.view(-1, args.eot, lc.shape[-1]).mean(dim=1)
+                        gd = (e.dx.cpu() - gc).double()
+                        out['parity_vs_oracle'] = {
+                            'rows': int(lc.shape[0]), 'max_abs_logit_err': float((e.logits.cpu() - lc).abs().max()),
+                            'argmax_agree': int((lg.argmax(dim=1).cpu() == ref_mean.argmax(dim=1)).sum()), 'images': int(ref_mean.shape[0]),
+                            'input_grad_rel_l2': float(gd.norm() / gc.double().norm()),
+                            'fused_cells': int(n_fused),
+                            'headline_fused_cells': int(headline_fused),
+                            'note': 'same inputs and latent noise as the cpu_baseline sample, replayed with the fused decoder cells forced '
+                                    'on (the kernels the timed chunk plans select); tolerance of the path: 1e-3 on logits'}
+                    out['cpu_baseline'] = cpu_baseline(model, 4 * args.eot, args.eot, check=parity)      # 128 rows: ~16 s of oracle time on 16 threads
+                    log('cpu baseline done')
+                    if args.robust_acc_images > 0:
+                        # robust accuracy under the reference's APGD-CE, HIP vs oracle, every draw pinned, with the paired 95 % interval of
+                        # the difference (the oracle as the checker, on a reduced model it can run hundreds of attacks on:
+                        # tests/robust_acc_attack.py; VERDICT r03 "next round" #3)
+                        log(f'robust accuracy under APGD-CE on {args.robust_acc_images} images (oracle on the host cores) ...')
+                        try:
+                            sys.path.insert(0, os.path.join(ROOT, 'tests'))
+                            from robust_acc_attack import robust_accuracy_under_attack
+                            free_gpu_memory()
+                            out['robust_accuracy_delta'] = robust_accuracy_under_attack(device, n_images=args.robust_acc_images, eot=2, n_iter=5,
+                                                                                        bound=2.0, chunk_images=min(64, args.robust_acc_images))
+                        except Exception as ex:
+                            out['robust_accuracy_delta'] = {'delta': None, 'what': f'failed: {type(ex).__name__}: {ex}'}
+                        log('robust-accuracy delta done')
+                except Exception as ex:   # the baseline is a reported number, never a reason to lose the bench line
+                    out['cpu_baseline'] = {'value': None, 'unit': 'rows/s', 'cores': 0, 'kind': 'port', 'sample': f'failed: {ex}'}
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()

@@ -86,6 +86,21 @@ def test_dlr_needs_four_classes():
 # the attacks batched over images.  Every image of a batch must come out as from its own one-image run
 # (which the goldens above pin to the reference), whatever the other images of the batch do: per-sample norms, masks, early
 # exits, step sizes, bests.
+def _one_image_at_a_time(net):
+    """the toy net applied to each image of a batch on its own: an image's logits and gradients are then bitwise those of a
+    one-image call, whatever the host's convolution kernels do for other batch sizes (they differ in the last bit, and a 20-step
+    APGD run turns such a difference into another step-size decision on some CPUs).  What the comparisons below see is the
+    attack's own batching: per-sample norms, masks, early exits, step sizes, bests."""
+    class PerImage(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.net = net
+
+        def forward(self, x):
+            return torch.cat([self.net(x[i:i + 1]) for i in range(x.shape[0])], dim=0)
+    return PerImage().eval()
+
+
 def _content_noise(image):
     """N(0,1) noise as a function of the image itself, so that batched and one-image runs draw the same noise per image"""
     out = []
@@ -99,7 +114,7 @@ def _content_noise(image):
 def test_batched_attack_equals_the_one_image_runs(name, gold, monkeypatch):
     from gen_adversarial_amd.attacks import l2_attacks
     monkeypatch.setattr(l2_attacks, '_per_image_randn', _content_noise)
-    net = toy_net()
+    net = _one_image_at_a_time(toy_net())
     images, labels = torch.from_numpy(gold['images']), torch.from_numpy(gold['labels'])
     # a fourth image that is misclassified from the start (returns success with distortion 0 and must not disturb the others)
     images = torch.cat([images, images[:1].flip(-1)], dim=0)
@@ -120,7 +135,7 @@ def test_batched_attack_equals_the_one_image_runs(name, gold, monkeypatch):
 def test_batched_autoattack_equals_the_one_image_runs(gold, monkeypatch):
     from gen_adversarial_amd.attacks import l2_attacks
     monkeypatch.setattr(l2_attacks, '_per_image_randn', _content_noise)
-    net = toy_net()
+    net = _one_image_at_a_time(toy_net())
     images, labels = torch.from_numpy(gold['images']), torch.from_numpy(gold['labels'])
 
     def make():

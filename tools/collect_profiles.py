@@ -44,7 +44,7 @@ for name, extra in (('1stream', ['--streams', '1']), ('2streams', [])):
     shutil.rmtree(d, ignore_errors=True)
     bj = os.path.join(OUT, f'bench_{name}.json')
     cmd = [ROCPROF, '--kernel-trace', '--stats', '--output-format', 'csv', '-d', d, '-o', name, '--'] + BENCH + \
-          ['--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-secondary', '--no-pmc'] + extra
+          ['--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-secondary', '--no-pmc'] + extra
     print('+', ' '.join(cmd), flush=True)
     with open(bj, 'w') as fo, open(os.path.join(OUT, f'bench_{name}.err'), 'w') as fe:
         rc = subprocess.run(cmd, stdout=fo, stderr=fe, env=env, cwd='/tmp').returncode
@@ -62,7 +62,7 @@ for name, extra in (('1stream', ['--streams', '1']), ('2streams', [])):
         g[1] += float(r['TotalDurationNs'])
     line = [ln for ln in open(bj).read().splitlines() if ln.startswith('{')]
     b = json.loads(line[-1]) if line else {}
-    md.append(f'## bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary --no-pmc {" ".join(extra)} under --kernel-trace --stats\n')
+    md.append(f'## bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-secondary --no-pmc {" ".join(extra)} under --kernel-trace --stats\n')
     if b:
         md.append(f'bench line under the profiler: {b["value"]:.0f} rows/s, roofline.avg_launch_ms {b["roofline"]["avg_launch_ms"]:.4f}, '
                   f'achieved {b["roofline"]["achieved"]:.1f} TFLOP/s (frac {b["roofline"]["frac"]:.4f})\n')
