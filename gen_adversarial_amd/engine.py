@@ -26,7 +26,7 @@ from .e4e_spec import E4ESpec
 from .resnet_spec import ResNetSpec
 from .vgg_spec import VggSpec
 from .engine_core import (IMG_LD, RES_SCALE, TUNE_FILE, WS_FLOATS, Act, WeightStore, _ptr, conv_key,  # noqa: F401
-                          tune_cache)
+                          frag_ok, halo_ok, thin_ok, tune_cache)
 from .engine_classifiers import ClassifierBuilder
 from .engine_e4e import E4EBuilder
 from .engine_avae import AvaeBuilder
@@ -463,14 +463,19 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
             need = splits * d.N * d.Ho * d.Wo * d.Cout
             if splits > 1 and (self.ws is None or need > WS_FLOATS):
                 tile, splits = 0, 1
-            if tile == 8 and not self._want_frag(d):    # conv_key does not encode pad / Wo / weight layout: a desc that shares the key of
-                tile = 5                                # a tile-8 entry without being eligible runs tile 5 (bitwise the same result)
-            if tile == 11 and (splits > 1 or not self._want_thin(d)):
-                tile, splits = 7, 1                     # (likewise: tile 7 gives tile 11's bits)
-            d.tile, d.splits = int(tile), int(splits)
-            d.ws, d.ws_floats = (_ptr(self.ws), WS_FLOATS) if splits > 1 else (None, 0)
             if not use_bf3:                      # this shape is faster on the exact fp32 kernel (small K or Cout)
                 d.w_hi, d.w_lo = None, None
+            # conv_key does not encode pad / Wo / the weight layout: a desc can share the key of a tile-8 or tile-11 entry without
+            # being eligible for that tile.  It then runs tile 5 (8) or 7 (11), which give the same bits, when the halo kernel
+            # takes it, else the library heuristic
+            if tile == 8 and not (self._want_frag(d) and frag_ok(d, splits)):
+                tile = 5
+            if tile == 11 and (splits > 1 or not (self._want_thin(d) and thin_ok(d, splits))):
+                tile, splits = 7, 1
+            if tile in (5, 6, 7) and not halo_ok(d, tile, splits):
+                tile, splits = 0, 1
+            d.tile, d.splits = int(tile), int(splits)
+            d.ws, d.ws_floats = (_ptr(self.ws), WS_FLOATS) if splits > 1 else (None, 0)
         self.fwd.finalize()
         self.bwd.finalize()
 

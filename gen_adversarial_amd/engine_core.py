@@ -37,6 +37,110 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
+# ---- which explicit tile codes ga_conv2d takes for a descriptor (GA_E_UNSUPPORTED otherwise).  A restatement of the checks in
+#      csrc/conv_mfma.hip (ga_conv2d: the split-bf16 and vector-output preconditions), csrc/conv_bf3.hip (conv_bf3_supports),
+#      csrc/conv_halo3.hip (conv_halo3_supports, halo_geometry, launch_halo, launch_halo_bd) and csrc/conv_thin3.hip
+#      (conv_thin3_supports); tests/test_plan_convs_gpu.py checks that the library refuses exactly what these reject.
+_HALO_HK, _HALO_LDH = 32, 40                # conv_halo3.hip: channels per chunk, bf16 per LDS pixel row
+_BF3_MODES = (0x000, 0x100, 0x001, 0x002, 0x003, 0x004, 0x010, 0x011, 0x020, 0x021)
+_HALO_MODES = (0x00, 0x01, 0x02, 0x03, 0x04, 0x10, 0x11, 0x20)
+
+
+def _a16(p) -> bool:
+    return not p or p % 16 == 0
+
+
+def _pro_mode(d) -> int:
+    return ((2 if d.pro_per_row else 1) if d.pro_scale else 0) << 4 | d.pro_act
+
+
+def _splits(d, splits=None) -> int:
+    s = d.splits if splits is None else splits
+    if s <= 1:
+        return 1
+    return min(s, d.KH * d.KW * ((d.C1 + d.C2 + 31) // 32))
+
+
+def _bf3_vec_out(d, splits: int) -> bool:
+    """the split-bf16 operands are usable (ga_conv2d's `bf3`) and the output is written as float4 (`vec_out`)"""
+    c2 = d.C2 > 0
+    vec = d.C1 % 4 == 0 and d.C2 % 4 == 0 and d.ldx % 4 == 0 and (not c2 or d.ldx2 % 4 == 0) and _a16(d.x) and _a16(d.w) \
+        and (not c2 or _a16(d.x2)) and (not d.pro_scale or (_a16(d.pro_scale) and _a16(d.pro_shift)))
+    bf3 = bool(d.w_hi and d.w_lo) and vec and d.sd == 1 and (not c2 or d.C1 % 32 == 0) and (d.C1 + d.C2) % 8 == 0 \
+        and d.KH * d.KW <= 32 and _a16(d.w_hi) and _a16(d.w_lo) and ((0x100 if c2 else 0) | _pro_mode(d)) in _BF3_MODES
+    vec_out = d.Cout % 4 == 0 and d.ldy % 4 == 0 and _a16(d.y) and _a16(d.bias) \
+        and (not d.addend or (d.ldadd % 4 == 0 and _a16(d.addend))) and (not d.addend2 or (d.ldadd2 % 4 == 0 and _a16(d.addend2))) \
+        and (not d.dact_x or (d.lddact % 4 == 0 and _a16(d.dact_x) and (not d.dact_scale or (_a16(d.dact_scale) and _a16(d.dact_shift))))) \
+        and (splits == 1 or _a16(d.ws))
+    return bf3 and vec_out
+
+
+def _halo_3x3(d) -> bool:
+    """conv_halo3_supports: 3x3 / stride 1 / pad 1, one source of C1 % 32 == 0 channels, 128-pixel tiles of whole rows (or whole
+    small images) or 128-pixel segments of one row"""
+    if (d.KH, d.KW, d.sn, d.sd, d.pad, d.C2) != (3, 3, 1, 1, 1, 0) or d.Ho != d.Hi or d.Wo != d.Wi or d.C1 % _HALO_HK:
+        return False
+    howo = d.Ho * d.Wo
+    rows = d.Wo < 128 and 128 % d.Wo == 0 and (howo % 128 == 0 or 128 % howo == 0)
+    return (rows or d.Wo % 128 == 0) and _pro_mode(d) in _HALO_MODES
+
+
+def _halo_geometry(d, bm: int = 128, ldh: int = _HALO_LDH):
+    """halo_geometry: (NI images per tile, P patch pixels, IS bf16 per image patch)"""
+    howo = d.Ho * d.Wo
+    wide = d.Wo >= bm
+    tw = bm if wide else d.Wo
+    th = 1 if wide else (bm // d.Wo if howo >= bm else d.Ho)
+    ni = 1 if howo >= bm else bm // howo
+    ph, pw = th + 2, tw + 2
+
+    def pad_to(nbytes, want):
+        return nbytes + ((want - nbytes) % 256 + 256) % 256
+    rs = pad_to(pw * ldh * 2, (tw * ldh * 2) % 256)
+    is_ = pad_to(ph * rs, (th * tw * ldh * 2) % 256) // 2
+    return ni, ni * ph * pw, is_
+
+
+def halo_ok(d, tile: Optional[int] = None, splits: Optional[int] = None) -> bool:
+    """ga_conv2d runs d on the LDS-staged halo kernel, tile 5 (128 x 128), 6 (128 x 64) or 7 (128 x 32; default d.tile)"""
+    tile = d.tile if tile is None else tile
+    s = _splits(d, splits)
+    if tile not in (5, 6, 7) or not _bf3_vec_out(d, s) or not _halo_3x3(d):
+        return False
+    ni, p, is_ = _halo_geometry(d)
+    if p > 13 * 32 or (p > 9 * 32 and _pro_mode(d) not in (0x00, 0x10, 0x20)) or s > d.C1 // _HALO_HK:
+        return False
+    bn = {5: 128, 6: 64, 7: 32}[tile]
+    return (2 * ni * is_ + 2 * 2 * bn * _HALO_LDH) * 2 <= 160 * 1024
+
+
+def frag_ok(d, splits: Optional[int] = None) -> bool:
+    """ga_conv2d runs d on tile 8: the halo kernel with its weight fragments read from d.w_frag"""
+    s = _splits(d, splits)
+    if not d.w_frag or not _a16(d.w_frag) or not _bf3_vec_out(d, s) or not _halo_3x3(d):
+        return False
+    ni, p, is_ = _halo_geometry(d)
+    if p > 9 * 32 or s > d.C1 // _HALO_HK:
+        return False
+    mode = _pro_mode(d)
+    patch = 2 * ni * is_ * 2
+    rp = (p * 8 + 255) >> 8
+    tab = rp * 256 * 6 + (2 * (ni if mode == 0x20 else 1) * d.C1 * 4 if mode >= 0x10 else 0)
+    dbuf = 2 * patch + tab <= 80 * 1024
+    tab_off = ((2 if dbuf else 1) * patch + 15) // 16 * 4
+    return tab_off * 4 + tab <= 80 * 1024
+
+
+def thin_ok(d, splits: Optional[int] = None) -> bool:
+    """ga_conv2d runs d on tile 11: the persistent weights-resident 3x3 kernel of 32 or 64 input channels (d.w_frag in its order)"""
+    s = _splits(d, splits)
+    if s != 1 or not d.w_frag or not _a16(d.w_frag) or not _bf3_vec_out(d, s):
+        return False
+    if (d.KH, d.KW, d.sn, d.sd, d.pad, d.C2) != (3, 3, 1, 1, 1, 0) or d.C1 not in (32, 64):
+        return False
+    return d.Ho == d.Hi and d.Wo == d.Wi and d.Ho % 8 == 0 and d.Wo % 16 == 0 and d.Wo <= 255 * 16 and _pro_mode(d) in _HALO_MODES
+
+
 class WeightStore:
     """Folded weights on the device, shared by every engine (row count) built for one model."""
 

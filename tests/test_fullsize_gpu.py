@@ -9,6 +9,7 @@ configs/ours_cosine_no_preprocessing_ids.yaml x 0.7 — the engine bench.py meas
     row independence (a 64-row plan equals two 32-row plans), and a directional-derivative check of the NVAE gradient.
 Tolerance 1e-3 absolute as BASELINE.json's north_star states; observed ~2e-5.
 """
+import gc
 import os
 
 import pytest
@@ -43,6 +44,10 @@ def model():
 
 
 def engine(m, rows, rep, **kw):
+    # an engine and its Act buffers reference each other: `del eng` frees its device memory only at the next cyclic collection,
+    # and two 1024-row plans do not fit beside each other
+    gc.collect()
+    torch.cuda.empty_cache()
     return Engine(m['sd'], ASSUMED_NVAE_CONFIG, ASSUMED_NVAE_RESOLUTION, m['vsd'], m['vspec'], rows=rows, rep=rep,
                   alphas=m['alphas'], temperature=0.6, noise_eps=0.0, device=DEV, store=m['store'], **kw)
 

@@ -525,3 +525,55 @@ def test_se_squeeze_of_few_large_rows_is_reduced_over_the_chip():
     assert Engine._se_wide_rows(32, 128 * 128, 64) and Engine._se_wide_rows(64, 32 * 32, 256)
     assert not Engine._se_wide_rows(1024, 128 * 128, 64)        # many rows: the fused form fills the chip
     assert not Engine._se_wide_rows(32, 64 * 64, 32) and not Engine._se_wide_rows(32, 16 * 16, 128)      # NVAE at 32 rows
+
+
+def _tuned_dry_conv(ho, wo, pad, c=32, cout=64, entry=(11, 1)):
+    """a dry-run engine holding one 3x3 conv with fake (aligned) split-weight pointers, tuned from a one-entry cache"""
+    from gen_adversarial_amd.engine_core import Act, conv_key
+    eng = Engine.bare(2, device='cpu', dry_run=True)
+    x, y = Act(eng, 2, ho + 2 - 2 * pad, wo + 2 - 2 * pad, c, 'x'), Act(eng, 2, ho, wo, cout, 'y')
+    w = torch.zeros(cout, 9 * c)
+    d = eng.conv(eng.fwd, 'c', x.t, w, y.t, K=3, pad=pad)
+    eng.finish()
+    d.w_hi, d.w_lo = 4096, 8192
+    eng.apply_tuning({conv_key(d): entry})
+    return d
+
+
+@pytest.mark.parametrize('entry', [(11, 1), (8, 1), (7, 1), (5, 2)])
+@pytest.mark.parametrize('ho,wo,pad', [(16, 48, 1), (16, 32, 0), (12, 16, 1), (8, 32, 1), (4, 256, 1)])
+def test_apply_tuning_never_picks_a_tile_the_library_refuses(entry, ho, wo, pad):
+    """conv_key does not encode Wo, pad or the weight layout, so a conv can share the key of a tile-11 / tile-8 entry without
+    being eligible for it.  apply_tuning falls back to the halo tiles only when the halo kernel takes the conv, else to tile 0"""
+    from gen_adversarial_amd.engine_core import frag_ok, halo_ok, thin_ok
+    d = _tuned_dry_conv(ho, wo, pad, entry=entry)
+    ok = {0: lambda: d.splits == 1, 5: lambda: halo_ok(d), 6: lambda: halo_ok(d), 7: lambda: halo_ok(d), 8: lambda: frag_ok(d),
+          11: lambda: thin_ok(d)}
+    assert ok[d.tile](), (entry, ho, wo, pad, d.tile, d.splits)
+    howo = ho * wo              # tiles of whole rows / whole images, or row segments
+    eligible = pad == 1 and ((wo < 128 and 128 % wo == 0 and (howo % 128 == 0 or 128 % howo == 0)) or wo % 128 == 0)
+    if eligible and entry[1] == 1:          # the fallback keeps the halo tile when the kernel takes the shape (same bits, fast)
+        assert d.tile == {11: 7, 8: 5, 7: 7}[entry[0]], d.tile
+
+
+def test_tile_predicates_follow_the_header():
+    """engine_core.halo_ok / frag_ok / thin_ok at the edges ga_conv_desc.tile documents"""
+    from types import SimpleNamespace
+    from gen_adversarial_amd.engine_core import frag_ok, halo_ok, thin_ok
+
+    def desc(ho, wo, c=32, pad=1, k=3, **kw):
+        base = dict(x=4096, x2=None, w=4096, bias=None, pro_scale=None, pro_shift=None, addend=None, addend2=None, dact_x=None,
+                    dact_scale=None, dact_shift=None, y=4096, ws=None, w_hi=4096, w_lo=4096, w_frag=4096, ldx=c, ldx2=0, ldy=64,
+                    ldadd=0, ldadd2=0, lddact=0, N=4, Hi=ho, Wi=wo, C1=c, C2=0, Ho=ho, Wo=wo, Cout=64, KH=k, KW=k, sn=1, sd=1,
+                    pad=pad, pro_act=0, pro_per_row=0, tile=7, splits=1)
+        base.update(kw)
+        return SimpleNamespace(**base)
+    assert halo_ok(desc(8, 16)) and halo_ok(desc(4, 256)) and halo_ok(desc(4, 4))
+    assert not halo_ok(desc(8, 48)) and not halo_ok(desc(8, 16, pad=0)) and not halo_ok(desc(8, 16, c=48))
+    assert not halo_ok(desc(8, 16, k=1)) and not halo_ok(desc(8, 16, w_hi=None)) and not halo_ok(desc(8, 16, sn=2))
+    assert not halo_ok(desc(2, 2))                      # 32 images of 4 x 4 patch pixels per tile: more than 13 * 32
+    assert not halo_ok(desc(4, 256, pro_act=1))         # row segments only for no prologue / affine / per-row affine
+    assert halo_ok(desc(8, 16, c=64, splits=2)) and not halo_ok(desc(8, 16, c=32, splits=2))   # split-K over 32-channel chunks
+    assert frag_ok(desc(8, 16)) and frag_ok(desc(16, 64)) and not frag_ok(desc(4, 128)) and not frag_ok(desc(8, 16, w_frag=None))
+    assert thin_ok(desc(8, 16)) and thin_ok(desc(16, 48, c=64)) and thin_ok(desc(8, 1024))
+    assert not thin_ok(desc(12, 16)) and not thin_ok(desc(8, 24)) and not thin_ok(desc(8, 16, c=96)) and not thin_ok(desc(8, 16, splits=2))

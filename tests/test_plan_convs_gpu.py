@@ -1,0 +1,405 @@
+"""
+Every dense contraction of the three shipped plans, as tuned, against the float64 interpreter of tests/convref.py.
+
+The engines are the ones bench.py times, built by the same code (configs[1] NVAE + VGG at bench.py's 1024-row chunk, the
+configs[2] e4e defender at 32 rows and the configs[4] Style-Transformer defender at 64 rows, EoT 32): apply_tuning makes its
+real choices only on a GPU (tile 8 / tile 11 need their weight fragments).  Each distinct ConvDesc of their forward and
+backward plans runs on buffers of this test with fewer rows, fresh weights and NaN-filled outputs, and must
+  - be accepted (GA_E_UNSUPPORTED on a shipped descriptor is a plan the engine would fail to run),
+  - meet |y - ref| <= tau * scale + slack + 2^-22 |ref| on every element (tau_bf3 / tau_fp32 of tests/convref.py),
+  - leave the channels [Cout, ldy) and a guard region past the last pixel NaN,
+  - give bitwise-equal results on two launches (split-K and every tile sum in a fixed order).
+The default run checks a deterministic subset: per class (tile, split-K, split-bf16, second source, transposed, flags,
+act' epilogue, addend) the descriptors of the smallest and the largest Wo.  GA_TEST_ALL_PLAN_CONVS=1 checks all of them.
+
+test_bound_catches_dropped_lo_weights shows, per tile, that the bound fails when the kernel runs on the bf16 weights alone.
+test_tile_eligibility_fuzz requests tiles 5 - 8 and 11 on shapes around their eligibility edges: the library refuses exactly
+what engine_core.halo_ok / frag_ok / thin_ok reject (the predicates apply_tuning relies on) and computes the rest correctly.
+"""
+import gc
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+if not torch.cuda.is_available():
+    pytest.skip('needs a GPU', allow_module_level=True)
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import convref as R                                                      # noqa: E402
+from gen_adversarial_amd import _lib as L                                # noqa: E402
+from gen_adversarial_amd.engine_core import WeightStore, frag_ok, halo_ok, thin_ok, _bf3_vec_out  # noqa: E402
+
+DEV = 'cuda:0'
+ALL = os.environ.get('GA_TEST_ALL_PLAN_CONVS', '0') == '1'
+GUARD = 256                                 # floats past the last output pixel that must stay NaN
+OPERANDS = ('x', 'x2', 'w', 'bias', 'pro_scale', 'pro_shift', 'addend', 'addend2', 'dact_x', 'dact_scale', 'dact_shift', 'y',
+            'w_hi', 'w_lo', 'w_frag', 'ws')
+INTS = tuple(f for f, _ in L.ConvDesc._fields_ if f not in OPERANDS + ('ws_floats', 'x_bytes', 'x2_bytes', 'w_bytes'))
+TILES = (0, 1, 2, 3, 4, 5, 6, 7, 8, 11)
+
+
+class Conv:
+    """one descriptor as the plan holds it: its integer fields, which operands it has, their 16-byte alignment (a pointer
+    offset changes the kernel's load path) and whether an addend aliases the output"""
+
+    def __init__(self, d, where=''):
+        self.f = {k: int(getattr(d, k)) for k in INTS}
+        self.has = frozenset(k for k in OPERANDS if getattr(d, k) and k not in ('ws', 'w_frag'))
+        self.frag = bool(d.w_frag) and d.tile in (8, 11)
+        self.align = tuple(sorted((k, getattr(d, k) % 16 // 4) for k in self.has))
+        self.alias = tuple(k for k in ('addend', 'addend2') if getattr(d, k) and getattr(d, k) == d.y)
+        self.where = [where]
+
+    def __getattr__(self, k):
+        f = self.__dict__.get('f')
+        if f is not None and k in f:
+            return f[k]
+        raise AttributeError(k)
+
+    @property
+    def key(self):
+        return tuple(sorted(self.f.items())), self.has, self.frag, self.align, self.alias
+
+    @property
+    def bf3(self):
+        return 'w_hi' in self.has
+
+    @property
+    def kdim(self):
+        return self.KH * self.KW * (self.C1 + self.C2)
+
+    def cls(self):
+        return (self.tile, self.splits > 1, self.bf3, self.C2 > 0, self.sd > 1, self.flags, 'dact_x' in self.has, 'addend' in self.has)
+
+    def label(self):
+        f = self
+        s = f'tile {f.tile:2d} split {f.splits:2d} {"bf3 " if f.bf3 else "fp32"} {f.N}x{f.Hi}x{f.Wi}x{f.C1}' + (f'+{f.C2}' if f.C2 else '')
+        s += f' -> {f.Ho}x{f.Wo}x{f.Cout} k{f.KH}x{f.KW} s{f.sn}/{f.sd} p{f.pad}'
+        extra = [k for k in ('pro_scale', 'dact_x', 'addend', 'addend2', 'bias') if k in self.has]
+        if f.flags:
+            extra.append(f'flags{f.flags}')
+        if f.pro_act:
+            extra.append(f'act{f.pro_act}')
+        if self.alias:
+            extra.append('in-place')
+        return s + (' [' + ','.join(extra) + ']' if extra else '')
+
+
+def _plan_convs(eng, plan_name, out):
+    for plan, tag in ((eng.fwd, 'fwd'), (eng.bwd, 'bwd')):
+        for d, name in zip(plan.descs, plan.names):
+            if isinstance(d, L.ConvDesc):
+                c = Conv(L.ConvDesc.from_buffer_copy(d), f'{plan_name}.{tag}.{name}')
+                if c.key in out:
+                    out[c.key].where.append(c.where[0])
+                else:
+                    out[c.key] = c
+
+
+@pytest.fixture(scope='module')
+def plan_convs():
+    """the distinct conv descriptors of the three shipped plans, by plan; the engines are built one at a time and freed"""
+    from bench import build_e4e_defender, build_model, build_trans_defender
+    builders = (('configs1_nvae', lambda: build_model(DEV, 1024, 32, seed=0, precision='bf16x3')[0]),
+                ('configs2_e4e', lambda: build_e4e_defender(DEV, 32, 32, 'bf16x3')[0]),
+                ('configs4_trans', lambda: build_trans_defender(DEV, 64, 32, 'bf16x3')[0]))
+    per_plan, every = {}, {}
+    for name, build in builders:
+        eng = build()
+        mine = {}
+        _plan_convs(eng, name, mine)
+        del eng
+        gc.collect()
+        torch.cuda.empty_cache()
+        per_plan[name] = len(mine)
+        for k, c in mine.items():
+            if k in every:
+                every[k].where += c.where
+            else:
+                every[k] = c
+    print(f'\nplan convs: {per_plan} distinct per plan, {len(every)} distinct over the three plans', flush=True)
+    return list(every.values())
+
+
+def _subset(convs):
+    """per class, the descriptors of the smallest and the largest Wo (ties broken by the full descriptor, deterministic)"""
+    by = {}
+    for c in convs:
+        by.setdefault(c.cls(), []).append(c)
+    pick = []
+    for k in sorted(by, key=repr):
+        v = sorted(by[k], key=lambda c: (c.Wo, repr(c.key)))
+        pick.append(v[0])
+        if len(v) > 1:
+            pick.append(v[-1])
+    return pick
+
+
+def _rows(c):
+    """a cheaper row count: a multiple of dact_rep, addend_rep and (small images) of the images per 128-pixel tile"""
+    m = 1
+    if 'dact_x' in c.has and c.dact_rep > 1:
+        m = math.lcm(m, c.dact_rep)
+    if 'addend' in c.has and not c.addend_bcast_n and c.addend_rep > 1:
+        m = math.lcm(m, c.addend_rep)
+    howo = c.Ho * c.Wo
+    if howo < 128:
+        m = math.lcm(m, -(-128 // howo))
+    return min(c.N, m) if c.N % m == 0 else c.N
+
+
+def _buf(n, off, fill, gen=None, scale=1.0):
+    """n floats starting `off` floats past a 256-byte aligned allocation"""
+    b = torch.empty(n + off, device=DEV)
+    v = b[off:]
+    if fill == 'nan':
+        v.fill_(float('nan'))
+    elif fill == 'randn':
+        v.normal_(0.0, scale, generator=gen)
+    elif fill == 'rand':
+        v.uniform_(0.5, 1.5, generator=gen)
+    return v
+
+
+def run_conv(c, n=None, seed=0, zero_lo=False, w=None):
+    """run descriptor c on fresh operands with n rows; -> (y buffer after launch 1, after launch 2, tensors for conv_ref, desc)
+    or raises L.GaError"""
+    n = c.N if n is None else n
+    gen = torch.Generator(device=DEV).manual_seed(seed)
+    al = dict(c.align)
+    d = L.ConvDesc()
+    for k, v in c.f.items():
+        setattr(d, k, v)
+    d.N = n
+    howo, pin = c.Ho * c.Wo, n * c.Hi * c.Wi
+    t = {}
+
+    def put(k, numel, fill, scale=1.0):
+        t[k] = _buf(numel, al.get(k, 0), fill, gen, scale)
+        setattr(d, k, t[k].data_ptr())
+    put('x', pin * c.ldx, 'randn')
+    if 'x2' in c.has:
+        put('x2', pin * c.ldx2, 'randn')
+    K = c.kdim
+    if w is None:
+        w = torch.randn(c.Cout, K, generator=gen, device=DEV) / math.sqrt(K)
+    t['w'] = _buf(c.Cout * K, al.get('w', 0), None)
+    t['w'].copy_(w.to(DEV).reshape(-1))
+    d.w = t['w'].data_ptr()
+    if 'bias' in c.has:
+        put('bias', c.Cout, 'randn', 0.5)
+    if 'pro_scale' in c.has:
+        m = n * c.C1 if c.pro_per_row else c.C1
+        put('pro_scale', m, 'rand')
+        put('pro_shift', m, 'randn', 0.5)
+    if 'dact_x' in c.has:
+        drep = c.dact_rep if c.dact_rep > 1 else 1
+        put('dact_x', n // drep * howo * c.lddact, 'randn')
+        if 'dact_scale' in c.has:
+            put('dact_scale', c.Cout, 'rand')
+            put('dact_shift', c.Cout, 'randn', 0.5)
+    y_numel = n * howo * c.ldy
+    y0 = _buf(y_numel + GUARD, 0, 'nan')
+    y_init = None
+    if c.alias:                         # in-place accumulation: y holds the addend on entry (channels < Cout)
+        y_init = y0.clone()
+        y_init[:y_numel].view(-1, c.ldy)[:, :c.Cout] = torch.randn(n * howo, c.Cout, generator=gen, device=DEV)
+    if 'addend' in c.has and 'addend' not in c.alias:
+        arep = c.addend_rep if c.addend_rep > 1 else 1
+        rows = 1 if c.addend_bcast_n else n // arep
+        put('addend', rows * howo * c.ldadd, 'randn')
+    if 'addend2' in c.has and 'addend2' not in c.alias:
+        put('addend2', n * howo * c.ldadd2, 'randn')
+    y = _buf(y_numel + GUARD, al.get('y', 0), 'nan')
+    d.y = y.data_ptr()
+    for k in c.alias:
+        setattr(d, k, d.y)
+        t[k] = y_init[:y_numel]
+    if c.splits > 1:
+        ws = _buf(c.splits * n * howo * c.Cout, 0, None)
+        d.ws, d.ws_floats = ws.data_ptr(), ws.numel()
+    if c.bf3:
+        wt = t['w'].view(c.Cout, K)
+        if zero_lo:                     # the kernel then computes with bf16 weights only
+            wt = wt.to(torch.bfloat16).float()
+        store = WeightStore(DEV)
+        hi, lo = store.split(wt)
+        d.w_hi, d.w_lo = hi.data_ptr(), lo.data_ptr()
+        t['_keep'] = [wt, hi, lo]
+        if c.frag:
+            fr = store.frag_thin(wt) if c.tile == 11 else store.frag3(wt)
+            d.w_frag = fr.data_ptr()
+            t['_keep'].append(fr)
+    stream = torch.cuda.current_stream().cuda_stream
+    outs = []
+    for _ in range(2):
+        src = y_init if y_init is not None else y0
+        y.copy_(src)
+        try:
+            L.run(d, stream)
+        except L.GaError as ex:     # a refused request launches nothing
+            torch.cuda.synchronize()
+            ex.untouched = torch.equal(y.view(torch.int32), src.view(torch.int32))
+            raise
+        torch.cuda.synchronize()
+        outs.append(y.clone())
+    t.pop('_keep', None)
+    t['y'] = y
+    return outs, t, d
+
+
+def check_conv(c, n=None, seed=0, zero_lo=False):
+    """-> (ratio to the bound, max |err| / scale, [failure messages])"""
+    n = _rows(c) if n is None else n
+    (y1, y2), t, d = run_conv(c, n, seed, zero_lo)
+    bad = []
+    howo, m = c.Ho * c.Wo, n * c.Ho * c.Wo
+    out = y1[:m * c.ldy].view(m, c.ldy)
+    if c.ldy > c.Cout and not torch.isnan(out[:, c.Cout:]).all():
+        bad.append('wrote channels >= Cout')
+    if not torch.isnan(y1[m * c.ldy:]).all():
+        bad.append('wrote past the last pixel')
+    if not torch.equal(y1.view(torch.int32), y2.view(torch.int32)):
+        bad.append('two launches differ')
+    ref, scale, slack = R.conv_ref(d, {k: v for k, v in t.items() if k != 'y'})
+    tau = R.TAU_BF3 if c.bf3 else R.TAU_FP32
+    r, e = R.bound_ratio(out[:, :c.Cout].reshape(n, c.Ho, c.Wo, c.Cout), ref, scale, slack, tau)
+    return r, e, bad
+
+
+def test_plan_conv_descriptors(plan_convs):
+    pick = plan_convs if ALL else _subset(plan_convs)
+    print(f'checking {len(pick)} of {len(plan_convs)} distinct conv descriptors ({len(plan_convs) - len(pick)} skipped'
+          f'{"" if ALL else "; GA_TEST_ALL_PLAN_CONVS=1 checks all"})', flush=True)
+    fails, worst = [], {}
+    for i, c in enumerate(pick):
+        try:
+            r, e, bad = check_conv(c, seed=i)
+        except L.GaError as ex:
+            fails.append(f'{c.label()} ({c.where[0]}): {ex}')
+            continue
+        tau = R.TAU_BF3 if c.bf3 else R.TAU_FP32
+        print(f'  {c.label():90s} n={_rows(c):4d}  max|err|/scale {e:.2e} = {e / tau:.3f} tau  bound {r:.3f}  {c.where[0]}', flush=True)
+        k = (c.tile, c.bf3)
+        worst[k] = max(worst.get(k, 0.0), e / tau)
+        if r > 1.0 or bad:
+            fails.append(f'{c.label()} ({c.where[0]}): bound ratio {r:.3g} {bad}')
+    for (tile, bf3), v in sorted(worst.items()):
+        print(f'  tile {tile:2d} {"bf3 " if bf3 else "fp32"}: worst max|err|/scale = {v:.3f} tau', flush=True)
+    assert not fails, '\n'.join(fails)
+
+
+def _synthetic(tile):
+    """a 3x3, 32 -> 64 conv on 8 x 16 images that every tile takes"""
+    d = L.ConvDesc()
+    d.N, d.Hi, d.Wi, d.C1, d.Ho, d.Wo, d.Cout, d.KH, d.KW, d.sn, d.sd, d.pad = 8, 8, 16, 32, 8, 16, 64, 3, 3, 1, 1, 1
+    d.ldx, d.ldy, d.tile, d.splits = 32, 64, tile, 1
+    d.x = d.w = d.y = d.w_hi = d.w_lo = 4096
+    d.w_frag = 4096 if tile in (8, 11) else None
+    return Conv(d, f'synthetic tile {tile}')
+
+
+def test_bound_catches_dropped_lo_weights(plan_convs):
+    """per tile, one split-bf16 descriptor (from the plans when they hold one: the shortest contraction) run with w_lo = 0:
+    the kernel then multiplies by bf16(w) alone and the bound must fail; the same descriptor with w_lo passes"""
+    msgs = []
+    for tile in TILES:
+        cands = [c for c in plan_convs if c.tile == tile and c.bf3 and c.splits == 1 and c.sd == 1 and _bf3_vec_out(_as_desc(c), 1)]
+        c = min(cands, key=lambda c: (c.kdim, repr(c.key))) if cands else _synthetic(tile)
+        r_ok, e_ok, bad = check_conv(c, seed=1)
+        r_lo, e_lo, _ = check_conv(c, seed=1, zero_lo=True)
+        print(f'  tile {tile:2d}: {c.label()}  bound {r_ok:.3f} -> {r_lo:.1f} without w_lo ({e_lo:.2e} of the scale)', flush=True)
+        if r_ok > 1.0 or bad:
+            msgs.append(f'tile {tile}: fails with w_lo ({r_ok:.3g}, {bad})')
+        if r_lo <= 1.0:
+            msgs.append(f'tile {tile}: the bound does not see the dropped w_lo ({r_lo:.3g})')
+    assert not msgs, '\n'.join(msgs)
+
+
+def _as_desc(c):
+    d = L.ConvDesc()
+    for k, v in c.f.items():
+        setattr(d, k, v)
+    for k in c.has:
+        setattr(d, k, 4096 + 4 * dict(c.align).get(k, 0))
+    return d
+
+
+def _fuzz_cases(n, seed):
+    rs = np.random.RandomState(seed)
+    out = []
+    while len(out) < n:
+        c = dict(Wo=int(rs.choice([16, 24, 32, 48, 64, 128, 256])), Ho=int(rs.choice([4, 6, 8, 12, 16])), C1=int(rs.choice([32, 48, 64, 96])),
+                 pad=int(rs.choice([0, 1, 1])), stride=int(rs.choice([1, 1, 1, 2])), x2=int(rs.choice([0, 0, 0, 32])),
+                 Cout=int(rs.choice([8, 40, 100, 130, 132, 257, 260])), N=int(rs.randint(1, 4)),
+                 pro=int(rs.choice([0, 0, 1, 2, 3])), act=int(rs.choice([0, 0, 1, 3])), splits=int(rs.choice([1, 1, 2])),
+                 addend=int(rs.randint(0, 2)), dact=int(rs.choice([0, 0, 1, 3])), seed=int(rs.randint(1 << 30)))
+        if c['Ho'] * c['Wo'] * c['N'] > 8192:
+            c['N'] = 1
+        out.append(c)
+    return out
+
+
+@pytest.mark.parametrize('c', _fuzz_cases(40, 955), ids=lambda c: 'N{N}_{Ho}x{Wo}_{C1}+{x2}to{Cout}_p{pad}s{stride}_pro{pro}a{act}_s{splits}'.format(**c))
+def test_tile_eligibility_fuzz(c):
+    """tiles 5, 6, 7, 8, 11 requested with their fragments built: refused (y untouched) exactly when the predicate says no,
+    else within the float64 bound"""
+    s, p = c['stride'], c['pad']
+    Hi, Wi = (c['Ho'] - 1) * s + 3 - 2 * p, (c['Wo'] - 1) * s + 3 - 2 * p
+    d = L.ConvDesc()
+    d.N, d.Hi, d.Wi, d.C1, d.C2, d.Ho, d.Wo, d.Cout = c['N'], Hi, Wi, c['C1'], c['x2'], c['Ho'], c['Wo'], c['Cout']
+    d.KH = d.KW = 3
+    d.sn, d.sd, d.pad, d.ldx, d.ldx2, d.ldy = s, 1, p, c['C1'], c['x2'], c['Cout']
+    d.x = d.w = d.y = d.w_hi = d.w_lo = 4096
+    if c['x2']:
+        d.x2 = 4096
+    d.bias = 4096
+    if c['pro']:
+        d.pro_scale = d.pro_shift = 4096
+        d.pro_per_row = int(c['pro'] == 2)
+        d.flags |= L.GA_CONV_PRO_PRELU if c['pro'] == 3 else 0
+    d.pro_act = c['act'] if c['pro'] != 3 else 0
+    if c['addend']:
+        d.addend, d.ldadd = 4096, c['Cout']
+    if c['dact']:
+        d.dact_x, d.lddact, d.dact_act = 4096, c['Cout'], c['dact']
+    d.splits = c['splits']
+    if c['splits'] > 1:
+        d.ws = 4096
+    fail = []
+    for tile in (5, 6, 7, 8, 11):
+        d.tile = tile
+        d.w_frag = 4096 if (tile == 8 and c['C1'] % 32 == 0 and not c['x2']) or (tile == 11 and c['C1'] in (32, 64) and not c['x2']) else None
+        conv = Conv(d, f'fuzz tile {tile}')
+        want = {8: frag_ok, 11: thin_ok}.get(tile, halo_ok)(d)
+        try:
+            r, e, bad = check_conv(conv, n=c['N'], seed=c['seed'])
+        except L.GaError as ex:
+            assert 'UNSUPPORTED' in str(ex), (tile, str(ex))
+            if not ex.untouched:
+                fail.append(f'tile {tile}: refused but wrote the output')
+            if want:
+                fail.append(f'tile {tile}: refused, the predicate says eligible')
+            continue
+        if not want:
+            fail.append(f'tile {tile}: accepted, the predicate says ineligible')
+        if r > 1.0 or bad:
+            fail.append(f'tile {tile}: bound ratio {r:.3g} (max|err|/scale {e:.2e}) {bad}')
+    assert not fail, '\n'.join(fail)
+
+
+def test_refused_request_leaves_the_output_untouched():
+    """a refused tile request launches nothing: the output keeps its NaN fill"""
+    c = _synthetic(11)
+    c.f['Wo'] = c.f['Wi'] = 24                      # tile 11 needs Wo % 16 == 0
+    for tile in (11, 8, 7):                         # the halo tiles need 128 % Wo == 0 or Wo % 128 == 0
+        c.f['tile'] = tile
+        with pytest.raises(L.GaError) as ex:
+            run_conv(c, n=2)
+        assert ex.value.untouched
