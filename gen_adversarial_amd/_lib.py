@@ -25,7 +25,7 @@ GA_CONV_ADDEND_RELU, GA_CONV_ADDEND_PRE_DACT, GA_CONV_PRO_PRELU, GA_CONV_DACT_PR
  GA_OP_MAXPOOL3S2, GA_OP_AVGPOOL_ACT, GA_OP_GCONV, GA_OP_PRELU, GA_OP_UNARY, GA_OP_MODOUT, GA_OP_UP2_BLUR, GA_OP_PIXELNORM,
  GA_OP_LATENT_MIX, GA_OP_POOL_DENORM, GA_OP_ATTN, GA_OP_LAYERNORM, GA_OP_RESIZE2_CROP, GA_OP_DEC_CELL, GA_OP_AVAE, GA_OP_DEC_CELL_HALO) = range(1, 31)
 GA_AVAE_ADAIN, GA_AVAE_AVGPOOL, GA_AVAE_PIXELNORM, GA_AVAE_SAMPLE = 0, 1, 2, 3
-ABI_VERSION = 7     # include/ga_ops.h: GA_ABI_VERSION (descriptor layouts + entry points); _load() refuses any other library
+ABI_VERSION = 8     # include/ga_ops.h: GA_ABI_VERSION (descriptor layouts + entry points); _load() refuses any other library
 ERRORS = {0: 'GA_OK', -1: 'GA_E_BADARG', -2: 'GA_E_ALIGN', -3: 'GA_E_UNSUPPORTED', -4: 'GA_E_LAUNCH'}
 
 fp = C.c_void_p     # device pointers travel as integers
@@ -79,7 +79,8 @@ class SamplerDesc(C.Structure):
                 ('z', fp), ('dz', fp), ('dmu_q', fp), ('dp', fp),
                 ('N', i32), ('h', i32), ('w', i32), ('NL', i32),
                 ('alpha', f32), ('one_minus_alpha', f32), ('temp', f32), ('backward', i32),
-                ('q_rep', i32), ('dmu_q_rows', fp), ('ldz', i32), ('act_rep', i32), ('mode', i32), ('_reserved', i32)]
+                ('q_rep', i32), ('dmu_q_rows', fp), ('ldz', i32), ('act_rep', i32), ('mode', i32), ('_reserved', i32),
+                ('alpha_rows', fp), ('alpha_ld', i32), ('alpha_col', i32)]
 
 
 class DmlDesc(C.Structure):
@@ -159,7 +160,7 @@ class PixelnormDesc(C.Structure):
 
 class LatentMixDesc(C.Structure):
     _fields_ = [('codes', fp), ('avg', fp), ('styles', fp), ('alpha', fp), ('out', fp), ('dout', fp), ('dcodes', fp),
-                ('R', i32), ('J', i32), ('D', i32), ('backward', i32), ('rep', i32), ('_reserved', i32)]
+                ('R', i32), ('J', i32), ('D', i32), ('backward', i32), ('rep', i32), ('alpha_ld', i32)]
 
 
 class PoolDenormDesc(C.Structure):

@@ -401,7 +401,11 @@ __global__ void __launch_bounds__(256) sampler_kernel(const ga_sampler_desc d, c
         const float ls = d.p ? d.p[apix * d.ldp + d.NL + c] : 0.f;
         const float e = d.eps_nchw ? d.eps[((size_t)na * d.NL + c) * hw + p] : d.eps[apix * d.NL + c];
         const float sig = d.temp * expf(softclamp5(ls));
-        const float a = d.alpha, om = d.one_minus_alpha;
+        float a = d.alpha, om = d.one_minus_alpha;
+        if (d.alpha_rows) {     // per-row pair, as the host stores it for the scalar fields (one broadcast load per row)
+            const float* ar = d.alpha_rows + (size_t)na * d.alpha_ld + 2 * d.alpha_col;
+            a = ar[0]; om = ar[1];
+        }
         if (!d.backward) {
             const float enc_mu = softclamp5(mp + mq);
             const float smp = e * sig + softclamp5(mp);
@@ -767,7 +771,15 @@ __global__ void __launch_bounds__(256) latent_mix_kernel(const ga_latent_mix_des
     const long row4 = (long)d.J * D4;                                  // quads per row
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long)gridDim.x * 256) {
         const int q = (int)(i % D4); const int j = (int)((i / D4) % d.J);
-        const float a = d.alpha[j];
+        if (d.alpha_ld > 0 && d.backward) {                            // per-row alphas: every replica's cotangent with its own (1 - alpha)
+            const long r0 = i / row4, off = i - r0 * row4;
+            floatx4 acc = {0.f, 0.f, 0.f, 0.f};
+            for (int k = 0; k < rep; ++k)
+                acc += (1.0f - d.alpha[(r0 * rep + k) * d.alpha_ld + j]) * ld4(d.dout + ((r0 * rep + k) * row4 + off) * 4);
+            *reinterpret_cast<floatx4*>(d.dcodes + i * 4) = acc;
+            continue;
+        }
+        const float a = d.alpha_ld > 0 ? d.alpha[(i / row4) * d.alpha_ld + j] : d.alpha[j];
         if (!d.backward) {                                             // i runs over the R output rows
             const long r = i / row4;
             floatx4 c = ld4(d.codes + ((r / rep) * row4 + (i - r * row4)) * 4);
@@ -1310,6 +1322,7 @@ extern "C" int ga_sampler_mix(const ga_sampler_desc* d, void* s) {
     if (d->act_rep > 1 && (!d->backward || d->N % d->act_rep || (d->q_rep > 1 && (d->N / d->act_rep) % d->q_rep))) return GA_E_BADARG;
     if (d->mode == 1 && (!d->p || d->ldq < 2 * d->NL || d->q_rep > 1 || (d->backward && (!d->dmu_q || !d->dp)))) return GA_E_BADARG;
     if (d->mode != 0 && d->mode != 1) return GA_E_UNSUPPORTED;
+    if (d->alpha_rows && (d->mode != 0 || d->alpha_col < 0 || d->alpha_ld < 2 * d->alpha_col + 2)) return GA_E_BADARG;
     const long total = (long)d->N * d->h * d->w * d->NL;
     hipLaunchKernelGGL(sampler_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, *d, total);
     return check_launch();
@@ -1430,6 +1443,7 @@ extern "C" int ga_latent_mix(const ga_latent_mix_desc* d, void* s) {
     if (!d->backward && (!d->codes || !d->styles || !d->out)) return GA_E_BADARG;
     if (d->backward && (!d->dout || !d->dcodes)) return GA_E_BADARG;
     if (d->rep > 1 && d->R % d->rep) return GA_E_BADARG;
+    if (d->alpha_ld != 0 && d->alpha_ld < d->J) return GA_E_BADARG;
     const long total4 = (long)(d->backward && d->rep > 1 ? d->R / d->rep : d->R) * d->J * (d->D / 4);
     hipLaunchKernelGGL(latent_mix_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)s, *d, total4);
     return check_launch();

@@ -134,7 +134,13 @@ class _EngineOwner:
     # of the differentiable engine
     supports_forward_only = False
 
-    def _engine(self, rows: int, rep: int, with_noise: bool = True, cot_rep: int = 1, forward_only: bool = False) -> Engine:
+    def _engine(self, rows: int, rep: int, with_noise: bool = True, cot_rep: int = 1, forward_only: bool = False,
+                alpha_rows: bool = False) -> Engine:
+        if alpha_rows:          # candidate-batched forward-only engine: its alphas are a per-row table the caller fills
+            key = (rows, rep, with_noise, 'alpha_rows')
+            if key not in self._engines:
+                self._engines[key] = self._make_engine(rows, rep, with_noise, need_backward=False, alpha_rows=True)
+            return self._engines[key]
         forward_only = forward_only and self.supports_forward_only and cot_rep == 1
         key = (rows, rep, with_noise) if cot_rep == 1 else (rows, rep, with_noise, cot_rep)
         if forward_only:
@@ -305,6 +311,38 @@ class MLVGMDefenseModel(ABC, _EngineOwner):
     def forward_rows(self, batch: torch.Tensor, rep: int = 1, preds_only: bool = True):
         logits, purified = self._run(batch, rep, not preds_only)
         return logits if preds_only else (logits, purified)
+
+    @torch.no_grad()
+    def forward_candidates(self, batch: torch.Tensor, alphas, rep: int = 1, preds_only: bool = True):
+        """K alpha vectors x `rep` EoT replicas of every image in ONE forward-only engine pass (the alpha-learning objective,
+        src/experiments/alpha_learning/common_utils.py:81-103, for K candidates at once): the encoder does not depend on the alphas
+        or on the latent draws, so it runs once per image and its K * rep rows read it.  alphas: [K, n] on the footing of
+        `interpolation_alphas` (attenuation already applied).  Returns logits [B, K, rep, classes] (and the purified images
+        [B, K, rep, 3, H, W]); every row has its own latent draw, rows ordered image-major, candidate, replica.
+        Not differentiable; refused with input noise configured (every row would be its own encoder input)."""
+        if self.eps != 0.0:
+            raise ValueError('candidate-batched evaluation shares the encoder pass of an image between its candidates and EoT '
+                             'replicas: not available on a defender with initial_noise_eps > 0')
+        if batch.dim() != 4 or batch.shape[1] != 3:
+            raise ValueError('expected a (B, 3, H, W) image batch')
+        a = alphas.detach().to('cpu', torch.float64) if isinstance(alphas, torch.Tensor) else torch.tensor(alphas, dtype=torch.float64)
+        if a.dim() != 2 or a.shape[1] != len(self.interpolation_alphas):
+            raise ValueError(f'[K, {len(self.interpolation_alphas)}] alphas expected, got {tuple(a.shape)}')
+        batch = batch.to(self.device, dtype=torch.float32).contiguous()
+        B, K = batch.shape[0], a.shape[0]
+        eng = self._engine(B * K * rep, K * rep, True, alpha_rows=True)
+        if tuple(batch.shape[2:]) != tuple(eng.resolution[1:]):
+            raise ValueError(f'expected {eng.resolution[1]}x{eng.resolution[2]} images, got {tuple(batch.shape[2:])}')
+        eng.set_alpha_rows(a)
+        eng.x_in.copy_(batch)
+        self._fill_noise(eng)
+        eng.forward()
+        eng.version += 1
+        logits = eng.logits.reshape(B, K, rep, -1).clone()
+        if preds_only:
+            return logits
+        purified = eng.purified.clone() if eng.purified is not None else eng.purified_nchw()
+        return logits, purified.view(B, K, rep, *purified.shape[1:])
 
     def purify(self, batch: torch.Tensor) -> torch.Tensor:
         """(B,3,H,W) pre-processed images -> purified reconstructions (no input noise / blur: those belong to

@@ -36,6 +36,25 @@ from .engine_stylegan import StyleGanBuilder
 from .engine_trans import TransBuilder
 
 
+def expand_alpha_rows(alphas, rows: int, rep: int, pairs: bool) -> torch.Tensor:
+    """[K, n] alpha vectors -> the float32 per-row table of an `alpha_rows` engine with `rows` rows, `rep` consecutive rows per image.
+    K == rows: one vector per row.  Otherwise K divides rep and the rows of every image are (candidate, replica)-ordered: row
+    (b * K + k) * E + e, E = rep / K, carries candidate k.  pairs: each alpha a is stored as (float(a), float(1.0 - a)), the
+    subtraction in double like the host does it for the scalar descriptor fields (ga_sampler_desc.one_minus_alpha); the table
+    is then [rows, 2 n], else [rows, n]."""
+    t = alphas.detach().to('cpu', torch.float64) if isinstance(alphas, torch.Tensor) else torch.tensor(alphas, dtype=torch.float64)
+    if t.dim() != 2:
+        raise ValueError(f'a [K, n] table of alpha vectors expected, got shape {tuple(t.shape)}')
+    K = t.shape[0]
+    if K != rows:
+        if K < 1 or rep % K or rows % rep:
+            raise ValueError(f'{K} candidates do not divide the {rep} rows per image')
+        t = t.repeat_interleave(rep // K, dim=0).repeat(rows // rep, 1)
+    if not pairs:
+        return t.to(torch.float32)
+    return torch.stack([t.to(torch.float32), (1.0 - t).to(torch.float32)], dim=2).reshape(rows, -1)
+
+
 class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuilder, StyleGanBuilder, TransBuilder):
     # decoder cells whose shape ga_dec_cell takes run as one fused launch per direction (GA_FUSE_DEC_CELL=0: the three
     # unfused launches, same numbers bit for bit — kept for A/B profiles and for the shapes the fused kernel refuses)
@@ -55,8 +74,11 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
                  alphas: Sequence[float], temperature: float = 0.6, noise_eps: float = 0.0,
                  device: str = 'cuda:0', need_backward: bool = True, dry_run: bool = False,
                  store: Optional[WeightStore] = None, precision: str = 'bf16x3', blur: bool = False,
-                 share_encoder: bool = False, cot_rep: int = 1):
-        """cot_rep = K > 1: the backward plan takes K cotangents per forward row in ONE replay (the per-class
+                 share_encoder: bool = False, cot_rep: int = 1, alpha_rows: bool = False):
+        """alpha_rows: the interpolation alphas are a per-row device table (`alpha_table`, filled by set_alpha_rows / set_alphas) read
+        by every sampler: rows of one image may carry different alpha vectors — K candidates x E EoT replicas with rep = K * E share
+        that image's encoder pass (alpha learning, src/experiments/alpha_learning/common_utils.py:81-103).
+        cot_rep = K > 1: the backward plan takes K cotangents per forward row in ONE replay (the per-class
         backward loops of DeepFool / FAB, src/attacks/untargeted.py:526-560, :605-635).  `dlogits` is then [rows * K, classes]
         (cotangent k of defender row r at row r * K + k) and `dx` [images * K, 3, H, W] (gradient k of image b at row b * K + k);
         every saved activation is read by its K cotangent rows, nothing is recomputed or copied."""
@@ -82,6 +104,7 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
         self.temperature = float(temperature)
         self.noise_eps = float(noise_eps)
         self.blur = bool(blur)
+        self._init_alpha_rows(alpha_rows)
         # EoT replicas of one image are identical until randomness enters.  Without input noise the whole encoder
         # (pre-processing + encoder tower + encoder_0 + sampler_0:0, ~57 % of the FLOPs) sees `rep` identical rows per
         # image: with share_encoder it runs once per IMAGE and its feature maps are read by all replicas of the decoder
@@ -107,7 +130,7 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
     @classmethod
     def bare(cls, rows: int, device='cuda:0', precision: str = 'bf16x3', store: Optional[WeightStore] = None,
              dry_run: bool = False, rep: int = 1, resolution=None, alphas: Sequence[float] = (), noise_eps: float = 0.0,
-             need_backward: bool = True, blur: bool = False, share_encoder: bool = False) -> "Engine":
+             need_backward: bool = True, blur: bool = False, share_encoder: bool = False, alpha_rows: bool = False) -> "Engine":
         """An engine with empty plans: building blocks that are not yet part of a full defender (the StyleGAN2 layers of
         engine_stylegan.py) are emitted into it by their builders and closed with `finish()`; forward() / backward() then
         replay the plans as for a full engine."""
@@ -121,6 +144,7 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
         self.has_nvae, self.spec, self.vspec, self.resolution = False, None, None, (tuple(resolution) if resolution else None)
         self.rows, self.rep, self.alphas, self.temperature = rows, rep, [float(a) for a in alphas], 1.0
         self.noise_eps, self.blur = float(noise_eps), bool(blur)
+        self._init_alpha_rows(alpha_rows)
         # EoT replicas are identical until randomness enters: without input noise an encoder in front of the first random
         # draw runs once per image (see Engine.__init__); builders that support it read share_encoder / enc_rows
         self.share_encoder = bool(share_encoder) and rep > 1 and self.noise_eps == 0.0
@@ -134,6 +158,20 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
     def finish(self):
         self._finish(0)
         return self
+
+    def _init_alpha_rows(self, alpha_rows: bool):
+        self.alpha_rows, self.alpha_table = bool(alpha_rows), None
+        if self.alpha_rows and self.rep > 1 and self.noise_eps != 0.0:
+            # candidates x replicas of an image share its encoder pass; input noise makes every row its own encoder input
+            raise ValueError('a per-row alpha engine with rep > 1 shares the encoder pass of an image between its rows: '
+                             'not available with input noise (initial_noise_eps > 0)')
+
+    def _alloc_alpha_table(self, n: int, pairs: bool) -> torch.Tensor:
+        """the per-row table [rows, 2 n] of (alpha, 1 - alpha) pairs (NVAE samplers) or [rows, n] (latent mixing), every row = self.alphas"""
+        self._alpha_pairs = pairs
+        self.alpha_table = self.alloc((self.rows, (2 if pairs else 1) * n))
+        self.alpha_table.copy_(expand_alpha_rows([self.alphas], self.rows, self.rows, pairs))
+        return self.alpha_table
 
     # ------------------------------------------------------------------------------------------------ memory
     def alloc(self, shape) -> torch.Tensor:
@@ -564,6 +602,10 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
         alphas = [float(a) for a in alphas]
         if len(alphas) != len(self.alphas):
             raise ValueError(f'{len(self.alphas)} interpolation alphas expected, got {len(alphas)}')
+        if self.alpha_table is not None:                     # per-row table: every row gets this vector (no descriptor changes)
+            self.alphas = alphas
+            self.alpha_table.copy_(expand_alpha_rows([alphas], self.rows, self.rows, self._alpha_pairs))
+            return
         if alphas == self.alphas:
             return
         self.alphas = alphas
@@ -576,6 +618,17 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
         self.bwd.finalize()
         if getattr(self, '_g_fwd', None) is not None:
             self.enable_graphs()                            # descriptors changed: re-capture
+
+    def set_alpha_rows(self, alphas):
+        """fill the per-row alpha table of an `alpha_rows` engine.  alphas: [rows, n] (one vector per row) or [K, n] candidates with
+        K dividing the engine's `rep`: the rep = K * E rows of an image are then candidate 0's E replicas, candidate 1's, ... (rows in the
+        order image-major, candidate, EoT replica).  Values as the samplers use them (attenuation already applied)."""
+        if self.alpha_table is None:
+            raise RuntimeError('engine was built without a per-row alpha table (alpha_rows=True)')
+        t = torch.as_tensor(alphas).detach().to('cpu', torch.float64) if isinstance(alphas, torch.Tensor) else torch.tensor(alphas, dtype=torch.float64)
+        if t.dim() != 2 or t.shape[1] != len(self.alphas):
+            raise ValueError(f'[K, {len(self.alphas)}] interpolation alphas expected, got {tuple(t.shape)}')
+        self.alpha_table.copy_(expand_alpha_rows(t, self.rows, self.rep, self._alpha_pairs))
 
     def stream(self) -> int:
         return torch.cuda.current_stream(self.device).cuda_stream

@@ -199,6 +199,8 @@ class NvaeBuilder:
         self.latent_pitch = (NL + 7) // 8 * 8
         self.eps = [self.alloc((R, NL, gs.res, gs.res)) for gs in spec.groups]   # NCHW like the reference draws them
         self.purified = self.alloc((R, 3, H, H))                            # NCHW
+        if self.alpha_rows:                       # per-row (alpha, 1 - alpha) pairs, one column pair per latent group
+            self._alloc_alpha_table(len(spec.groups), pairs=True)
 
         # ---- stem: normalisation (x-0.5)/0.5 as prologue affine, then weight-normed 3x3 (model.py:106-107)
         stem = self.devd('stem', lambda: F.pad_image_conv(F.fold_wn_conv(nvae_sd, 'preprocessing_block.init_conv'), 3, IMG_LD))
@@ -316,6 +318,7 @@ class NvaeBuilder:
         d.eps, d.eps_nchw, d.z = _ptr(eps), 1, _ptr(z.t)
         d.N, d.h, d.w, d.NL, d.ldz = z.n, z.h, z.w, self.spec.num_latent, z.c
         d.alpha, d.one_minus_alpha, d.temp, d.backward = alpha, 1.0 - alpha, self.temperature, 0
+        self._sampler_alpha_rows(d, eps)
         d.q_rep = q_rep
         self._sampler_descs.append((d, [i for i, e in enumerate(self.eps) if e is eps][0]))
         self.fwd.add(d, name)
@@ -337,11 +340,17 @@ class NvaeBuilder:
             d.dmu_q = _ptr(muq.g)
         d.N, d.h, d.w, d.NL, d.ldz, d.act_rep = nc, z.h, z.w, self.spec.num_latent, z.c, self.cot_rep
         d.alpha, d.one_minus_alpha, d.temp, d.backward = alpha, 1.0 - alpha, self.temperature, 1
+        self._sampler_alpha_rows(d, eps)
         self._sampler_descs.append((d, [i for i, e in enumerate(self.eps) if e is eps][0]))
         self.bwd.add(d, name)
         if q_rep > 1:
             self.rep_sum(name + '.rep_sum', rows_grad, muq, q_rep)
         muq.g_written = True
+
+    def _sampler_alpha_rows(self, d, eps):
+        if self.alpha_table is not None:
+            d.alpha_rows, d.alpha_ld = _ptr(self.alpha_table), self.alpha_table.shape[1]
+            d.alpha_col = [i for i, e in enumerate(self.eps) if e is eps][0]
 
     def rep_sum(self, name, x_rows: torch.Tensor, target: Act, rep: int):
         """target.g (+)= sum over the `rep` replicas of x_rows (gradient of a tensor shared by the EoT replicas)"""

@@ -237,18 +237,22 @@ class StyleGanBuilder:
         self.eps = [self.alloc((R, J, D))]
         styles = self.build_mapping(gsd, self.eps[0].view(R * J, D))
         avg = self.devd('sg.latent_avg', lambda: {'a': latent_avg.reshape(J, D)})['a'] if latent_avg is not None else None
-        self.alpha_dev = self.alloc((J,))
-        self.alpha_dev.copy_(torch.tensor(self.alphas, dtype=torch.float32))
+        if self.alpha_rows:                                      # per-row alphas [R, J] (Engine.set_alpha_rows)
+            self.alpha_dev, alpha_src, alpha_ld = None, self._alloc_alpha_table(J, pairs=False), J
+        else:
+            self.alpha_dev = alpha_src = self.alloc((J,))
+            self.alpha_dev.copy_(torch.tensor(self.alphas, dtype=torch.float32))
+            alpha_ld = 0
         latent = Act(self, R, 1, 1, J * D, 'sg.latent')
         mx = L.LatentMixDesc()
-        mx.codes, mx.avg, mx.styles, mx.alpha, mx.out = _ptr(codes), _ptr(avg), _ptr(styles), _ptr(self.alpha_dev), _ptr(latent.t)
-        mx.R, mx.J, mx.D, mx.backward, mx.rep = R, J, D, 0, R // self.enc_rows
+        mx.codes, mx.avg, mx.styles, mx.alpha, mx.out = _ptr(codes), _ptr(avg), _ptr(styles), _ptr(alpha_src), _ptr(latent.t)
+        mx.R, mx.J, mx.D, mx.backward, mx.rep, mx.alpha_ld = R, J, D, 0, R // self.enc_rows, alpha_ld
         self.fwd.add(mx, 'latent_mix')
 
         def bwd_mix():
             b = L.LatentMixDesc()
-            b.alpha, b.dout, b.dcodes, b.R, b.J, b.D, b.backward = _ptr(self.alpha_dev), _ptr(latent.g), _ptr(dcodes), R, J, D, 1
-            b.rep = R // self.enc_rows
+            b.alpha, b.dout, b.dcodes, b.R, b.J, b.D, b.backward = _ptr(alpha_src), _ptr(latent.g), _ptr(dcodes), R, J, D, 1
+            b.rep, b.alpha_ld = R // self.enc_rows, alpha_ld
             self.bwd.add(b, 'latent_mix^T')
         self._bwd_steps.append(bwd_mix)
 

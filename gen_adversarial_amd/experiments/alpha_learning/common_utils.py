@@ -1,8 +1,9 @@
 """
 Alpha-learning objective on the fast forward path (reference: src/experiments/alpha_learning/common_utils.py:15-103).
 `AlphaEvaluator.objective_function(alphas)` = EoT-32 accuracy of the defender, with the given interpolation alphas, on
-a pre-computed adversarial set.  The reference walks the set one image at a time; here `batch_images` images x 32 EoT
-rows go through the engine per call (the objective is forward-only and embarrassingly parallel over images).
+a pre-computed adversarial set, for the three defenders.  The reference walks the set one image at a time; here `batch_images`
+images x 32 EoT rows go through the engine per call (the objective is forward-only and embarrassingly parallel over images), and
+`objective_many` scores several alpha vectors per call: the candidates and EoT replicas of an image share its encoder pass.
 BoTorch-based Bayesian optimisation stays third-party and is not reproduced; `random_search` is grid_search.py:44-72.
 """
 from __future__ import annotations
@@ -13,7 +14,8 @@ from typing import Sequence
 import numpy as np
 import torch
 
-from ...defenses.ours.models import CelebaIdentityClassifier, NVAEDefenseModel
+from ...defenses.ours.models import (CarsTypeClassifier, CelebaGenderClassifier, CelebaIdentityClassifier, E4EStyleGanDefenseModel,
+                                      NVAEDefenseModel, TransStyleGanDefenseModel)
 from ...defenses.wrappers import EoTWrapper
 
 
@@ -31,21 +33,35 @@ def get_best_combination(folder: str) -> np.ndarray:
     return alphas[accuracies.argmax()]
 
 
+# classifier_type -> (classifier class, defender class, number of alphas, alpha attenuation, image size): the reference's three
+# branches (src/experiments/alpha_learning/common_utils.py:39-70)
+DEFENDERS = {'vgg-11': (CelebaIdentityClassifier, NVAEDefenseModel, 24, 0.7, 64),
+             'resnet-50': (CelebaGenderClassifier, E4EStyleGanDefenseModel, 18, 1.0, 256),
+             'resnext-50': (CarsTypeClassifier, TransStyleGanDefenseModel, 16, 0.7, 128)}
+
+# Rows (images x candidates x EoT replicas) of one candidate-batched engine pass.  The shipped NVAE conv plans are tuned for 1024-row
+# chunks, so the default fills one: batch_images = 8 at EoT 32 gives 4 candidates per pass.  The StyleGAN defenders
+# decode at 1024 / 512 px, where the activations of 256 rows are what a pass can hold: they default to one candidate per pass.
+ROW_BUDGET = {'vgg-11': 1024, 'resnet-50': 256, 'resnext-50': 256}
+
+
 class AlphaEvaluator:
     def __init__(self, args, device, images: torch.Tensor = None, labels: torch.Tensor = None, batch_images: int = 8):
-        """args: classifier_type ('vgg-11' is the built path), classifier_path, autoencoder_path, [adv_images_path]."""
+        """args: classifier_type ('vgg-11' | 'resnet-50' | 'resnext-50'), classifier_path, autoencoder_path, [adv_images_path];
+        optional initial_alphas (its length = the number of alphas of a reduced checkpoint) and eot_steps."""
         self.device = device
         self.eot_steps = 32
         self.batch_images = batch_images
-        if args.classifier_type != 'vgg-11':
-            raise NotImplementedError(f"classifier type {args.classifier_type}: StyleGAN paths are next rows")
-        args.image_size = 64
-        self.alpha_attenuation = 0.7
-        base = CelebaIdentityClassifier(args.classifier_path, device)
-        n = len(getattr(args, 'initial_alphas', [0.] * 24))
-        self.defense_model = NVAEDefenseModel(base, args.autoencoder_path, [0. for _ in range(n)],
-                                              alpha_attenuation=0.7, device=device).eval()
-        self.defense_model = EoTWrapper(self.defense_model, getattr(args, 'eot_steps', self.eot_steps)).eval()
+        if args.classifier_type not in DEFENDERS:
+            raise ValueError(f'Unknown classifier type: {args.classifier_type}')
+        classifier, defender, n_alphas, self.alpha_attenuation, args.image_size = DEFENDERS[args.classifier_type]
+        self.classifier_type = args.classifier_type
+        base = classifier(args.classifier_path, device)
+        n = len(getattr(args, 'initial_alphas', [0.] * n_alphas))
+        self.defense_model = defender(base, args.autoencoder_path, [0. for _ in range(n)],
+                                      alpha_attenuation=self.alpha_attenuation, device=device).eval()
+        self.eot_steps = getattr(args, 'eot_steps', self.eot_steps)
+        self.defense_model = EoTWrapper(self.defense_model, self.eot_steps).eval()
         if images is None:
             from ..test_defense import folder_dataset
             images, labels = folder_dataset(args.adv_images_path, args.image_size)
@@ -66,15 +82,45 @@ class AlphaEvaluator:
     def objective_function(self, alphas: Sequence[float]) -> float:
         return torch.mean(self.per_image_verdicts(alphas).to(torch.float32)).item()
 
+    def default_candidates_per_pass(self) -> int:
+        """candidates per engine pass from the row budget: ROW_BUDGET // (batch_images x EoT), at least 1"""
+        return max(1, ROW_BUDGET[self.classifier_type] // (self.batch_images * self.eot_steps))
+
+    @torch.no_grad()
+    def per_image_verdicts_many(self, alphas, candidates_per_pass: int = None) -> np.ndarray:
+        """[K, n] alpha vectors -> bool [K, N]: row k = per_image_verdicts(alphas[k]) with fresh draws.  `candidates_per_pass`
+        candidates x `batch_images` images x EoT rows go through the engine per call; the encoder runs once per image of a call,
+        every (image, candidate, replica) row has its own latent draws, the EoT mean is over each candidate's own replicas."""
+        a = alphas.detach().to('cpu', torch.float64) if isinstance(alphas, torch.Tensor) else torch.tensor(np.asarray(alphas), dtype=torch.float64)
+        if a.dim() != 2:
+            raise ValueError(f'[K, n] alphas expected, got {tuple(a.shape)}')
+        a = a * self.alpha_attenuation                       # in double, like `a * alpha_attenuation` on the list (:88)
+        cpp = self.default_candidates_per_pass() if candidates_per_pass is None else int(candidates_per_pass)
+        if cpp < 1:
+            raise ValueError('candidates_per_pass must be at least 1')
+        model = self.defense_model.model
+        out = np.zeros((a.shape[0], self.images.shape[0]), dtype=bool)
+        for k0 in range(0, a.shape[0], cpp):
+            cand = a[k0:k0 + cpp]
+            for i in range(0, self.images.shape[0], self.batch_images):
+                x, y = self.images[i:i + self.batch_images], self.labels[i:i + self.batch_images]
+                logits = model.forward_candidates(x, cand, rep=self.eot_steps)            # [B, k, EoT, classes]
+                pred = logits.mean(dim=2).argmax(dim=2)                                   # [B, k]
+                out[k0:k0 + cand.shape[0], i:i + x.shape[0]] = torch.eq(pred, y.view(-1, 1)).t().cpu().numpy()
+        return out
+
+    @torch.no_grad()
+    def objective_many(self, alphas, candidates_per_pass: int = None) -> np.ndarray:
+        """[K, n] alpha vectors -> float32 [K]: objective_function of every candidate"""
+        return self.per_image_verdicts_many(alphas, candidates_per_pass).astype(np.float32).mean(axis=1)
+
 
 @torch.no_grad()
-def random_search(evaluator: AlphaEvaluator, n_steps: int, seed: int = 0):
-    """uniform random alphas, keep all (alphas, accuracy) pairs — grid_search.py:44-72"""
+def random_search(evaluator: AlphaEvaluator, n_steps: int, seed: int = 0, candidates_per_pass: int = None):
+    """uniform random alphas, keep all (alphas, accuracy) pairs — grid_search.py:44-72; the candidates are scored
+    `candidates_per_pass` at a time (AlphaEvaluator.objective_many)"""
     n = len(evaluator.defense_model.model.interpolation_alphas)
     g = torch.Generator().manual_seed(seed)
-    all_alphas, all_acc = [], []
-    for _ in range(n_steps):
-        alphas = torch.rand(n, generator=g)
-        all_alphas.append(alphas)
-        all_acc.append(evaluator.objective_function(alphas))
-    return torch.stack(all_alphas).numpy(), np.asarray(all_acc, dtype=np.float32).reshape(-1, 1)
+    all_alphas = torch.stack([torch.rand(n, generator=g) for _ in range(n_steps)])
+    acc = evaluator.objective_many(all_alphas, candidates_per_pass)
+    return all_alphas.numpy(), np.asarray(acc, dtype=np.float32).reshape(-1, 1)

@@ -229,6 +229,11 @@ typedef struct ga_sampler_desc {
                           backward writes dmu_q [N,h,w,ldq] and dp [N,h,w,ldp], channels [0, 2 NL) (the two are equal: the
                           parameters enter as sums).  alpha, temp, q_rep unused. */
     int _reserved;
+    const float* alpha_rows;   /* mode 0, optional: per-row interpolation weights.  Row n reads the pair (alpha, one_minus_alpha) at
+                                  alpha_rows[n*alpha_ld + 2*alpha_col + {0, 1}] instead of the scalar fields (both numbers are stored, as
+                                  the host computes them for the scalar fields: equal alphas give bitwise the scalar path's results).
+                                  With act_rep > 1 the table is indexed by the forward row n / act_rep.  alpha_ld >= 2*alpha_col + 2 */
+    int alpha_ld; int alpha_col;
 } ga_sampler_desc;
 int ga_sampler_mix(const ga_sampler_desc* d, void* stream);
 
@@ -322,13 +327,15 @@ int ga_pixelnorm(const float* x, float* y, long rows, int C, void* stream);
 /* Latent mixing of the e4e defender (src/defenses/ours/models.py:116-127 + pSp.encode's latent_avg, psp.py:93-103):
  *   forward : out[r, j, :] = (1 - alpha[j]) * (codes[r, j, :] + avg[j, :]) + alpha[j] * styles[r, j, :]
  *   backward: dcodes[r, j, :] = (1 - alpha[j]) * dout[r, j, :]
- * styles / out / dout: [R, J, D]; codes / dcodes: [R / max(rep, 1), J, D]; avg: [J, D] or NULL; alpha: [J] (device).  D % 4 == 0. */
+ * styles / out / dout: [R, J, D]; codes / dcodes: [R / max(rep, 1), J, D]; avg: [J, D] or NULL; alpha: [J] (device).  D % 4 == 0.
+ * alpha_ld > 0: alpha is a per-row table [R][alpha_ld], alpha_ld >= J, row r uses alpha[r*alpha_ld + j]; dcodes then sums the
+ * replicas' cotangents in row order, each scaled by its own (1 - alpha). */
 typedef struct ga_latent_mix_desc {
     const float* codes; const float* avg; const float* styles; const float* alpha; float* out;
     const float* dout; float* dcodes; int R, J, D; int backward;
     int rep;      /* > 1: codes / dcodes have R / rep rows — the encoder ran once per image and its `rep` EoT replicas (consecutive
                      rows) share the codes; dcodes sums the replicas' cotangents in row order.  0 or 1: one code row per row */
-    int _reserved;
+    int alpha_ld; /* 0: alpha is [J], shared by all rows.  > 0: row pitch of the per-row table (see above) */
 } ga_latent_mix_desc;
 int ga_latent_mix(const ga_latent_mix_desc* d, void* stream);
 
@@ -610,7 +617,7 @@ long ga_debug_set_conv_row_limit(long bytes);
 const char* ga_last_hip_error(void);
 /* GA_ABI_VERSION is bumped with EVERY change of a descriptor's layout or meaning (a field added, a reserved field put to use) and
  * with every entry point added; the binding (gen_adversarial_amd/_lib.py: ABI_VERSION) refuses a library that reports another one. */
-#define GA_ABI_VERSION 7
+#define GA_ABI_VERSION 8
 int ga_abi_version(void);
 unsigned long ga_sizeof_op(void);
 
