@@ -4,7 +4,8 @@ Alpha-learning objective on the fast forward path (reference: src/experiments/al
 a pre-computed adversarial set, for the three defenders.  The reference walks the set one image at a time; here `batch_images`
 images x 32 EoT rows go through the engine per call (the objective is forward-only and embarrassingly parallel over images), and
 `objective_many` scores several alpha vectors per call: the candidates and EoT replicas of an image share its encoder pass.
-BoTorch-based Bayesian optimisation stays third-party and is not reproduced; `random_search` is grid_search.py:44-72.
+`random_search` is grid_search.py:44-72; the Bayesian optimisation (bayesian_optimization.py, on the project's own Gaussian-process
+surrogate in gp.py instead of BoTorch) proposes `objective_many`-sized rounds.
 """
 from __future__ import annotations
 
