@@ -27,25 +27,58 @@ __global__ void __launch_bounds__(256) avae_adain_kernel(const ga_avae_desc d, c
     const float* nz = d.a ? d.a + (size_t)n * d.P : nullptr;
     const floatx4 wn = (cok && d.b) ? *reinterpret_cast<const floatx4*>(d.b + c) : zero;
     if (!d.backward) {
-        floatx4 s1 = zero, s2 = zero;
-        if (cok)
+        // InstanceNorm2d's variance is the mean of (u - mean)^2; E[u^2] - mean^2 in fp32 loses its digits when a channel's mean is
+        // large against its spread (8 sigma: 64 x the rounding error).  So: the mean first, summed around u0 = the row's first
+        // pixel (keeps the mean's own digits), then the squares around the mean; each sum in the fixed order of before.
+        floatx4 s1 = zero, u0 = zero;
+        if (cok) {
+            u0 = *reinterpret_cast<const floatx4*>(t + c);
+            if (nz) u0 += wn * nz[0];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) u0[e] = lrelu02(u0[e]);
             for (int p = pl; p < d.P; p += 32) {
                 floatx4 u = *reinterpret_cast<const floatx4*>(t + (size_t)p * d.C + c);
                 if (nz) u += wn * nz[p];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) u[e] = lrelu02(u[e]);
-                s1 += u; s2 += u * u;
+                s1 += u - u0;
             }
+        }
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { red[0][pl][4 * c4 + e] = s1[e]; red[1][pl][4 * c4 + e] = s2[e]; }
+        for (int e = 0; e < 4; ++e) red[0][pl][4 * c4 + e] = s1[e];
+        if (pl == 0)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sm_a[4 * c4 + e] = u0[e];
         __syncthreads();
         if (tid < 32) {
-            float a = 0.f, b = 0.f;
-            for (int k = 0; k < 32; ++k) { a += red[0][k][tid]; b += red[1][k][tid]; }
-            const float mean = a / (float)d.P;
-            const float var = fmaxf(b / (float)d.P - mean * mean, 0.f);
-            const float rstd = rsqrtf(var + 1e-5f);
-            sm_mean[tid] = mean; sm_rstd[tid] = rstd;
+            float a = 0.f;
+            for (int k = 0; k < 32; ++k) a += red[0][k][tid];
+            sm_mean[tid] = sm_a[tid] + a / (float)d.P;
+        }
+        __syncthreads();
+        floatx4 s2 = zero;
+        if (cok) {
+            floatx4 m;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) m[e] = sm_mean[4 * c4 + e];
+            for (int p = pl; p < d.P; p += 32) {
+                floatx4 u = *reinterpret_cast<const floatx4*>(t + (size_t)p * d.C + c);
+                if (nz) u += wn * nz[p];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) u[e] = lrelu02(u[e]);
+                u -= m;
+                s2 += u * u;
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) red[1][pl][4 * c4 + e] = s2[e];
+        __syncthreads();
+        if (tid < 32) {
+            float b = 0.f;
+            for (int k = 0; k < 32; ++k) b += red[1][k][tid];
+            const float mean = sm_mean[tid];
+            const float rstd = rsqrtf(b / (float)d.P + 1e-5f);
+            sm_rstd[tid] = rstd;
             const int cc = chunk * 32 + tid;
             if (cc < d.C) { d.y2[((size_t)n * d.C + cc) * 2] = mean; d.y2[((size_t)n * d.C + cc) * 2 + 1] = rstd; }
         }

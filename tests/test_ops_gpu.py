@@ -1,7 +1,18 @@
 """
-GPU parity tests, one per C entry point of include/ga_ops.h: each kernel against the same op written with plain
+GPU parity tests of the C entry points of include/ga_ops.h: each kernel against the same op written with plain
 PyTorch fp32 on the CPU (forward and, through autograd, backward-to-input).  Tolerances are stated per test;
 the dense contractions are exact-fp32 fma chains whose summation order differs from ATen's, hence ~1e-5 relative.
+
+Entry points and fields that are not tested here:
+  tests/test_ops_edges_gpu.py   against the float64 references of tests/opref.py: ga_avae, ga_unary, ga_prelu, ga_pixelnorm,
+                                ga_axpby, ga_pool_denorm, interleaved ga_modout, shared-alpha ga_latent_mix, ga_sampler_mix
+                                mode 1, the replica fields act_rep / dact_rep / cot_rep, odd and non-square images, and the
+                                second trip of every capped grid
+  tests/test_plan_convs_gpu.py  every tuned convolution of the shipped plans against tests/convref.py
+  tests/test_dec_cell_gpu.py, tests/test_dec_cell_halo_gpu.py       ga_dec_cell, ga_dec_cell_halo
+  tests/test_alpha_search_gpu.py                                    per-row alpha tables of ga_sampler_mix / ga_latent_mix
+  tests/test_stylegan_gpu.py, tests/test_trans_gpu.py, tests/test_resnet_gpu.py   ga_up2_blur, ga_attn, ga_layernorm,
+                                ga_resize2_crop and the remaining pieces inside their models
 """
 import ctypes as C
 
