@@ -428,6 +428,8 @@ int conv_halo3_dispatch(const ga_conv_desc& d, hipStream_t stream, int tile, int
 int conv_halo3_supports(const ga_conv_desc& d);
 int conv_thin3_dispatch(const ga_conv_desc& d, hipStream_t stream, int vec_out, int splits);             // conv_thin3.hip
 int conv_thin3_supports(const ga_conv_desc& d);
+int conv_pw_frag_dispatch(const ga_conv_desc& d, hipStream_t stream, int vec_out);                       // conv_pw_frag.hip
+int conv_pw_frag_supports(const ga_conv_desc& d, int splits);
 
 }  // namespace ga
 
@@ -550,6 +552,9 @@ extern "C" int ga_conv2d(const ga_conv_desc* dp, void* stream_) {
     if (tile == 11) {                   // persistent weights-resident 3x3 for 32 input channels (explicit request only; w_frag in the thin order)
         if (!(bf3 && vec_out && conv_thin3_supports(d))) return GA_E_UNSUPPORTED;
         rc = conv_thin3_dispatch(k, stream, vec_out, splits);
+    } else if (tile == 12) {            // 1x1 with the weight fragments read from global memory (explicit request only; w_frag with one tap)
+        if (!(bf3 && vec_out && conv_pw_frag_supports(d, splits))) return GA_E_UNSUPPORTED;
+        rc = conv_pw_frag_dispatch(k, stream, vec_out);
     } else if (tile >= 5 && tile <= 10) {      // halo-staged 3x3 (explicit request only: the tune table names it per shape)
         if (!(bf3 && vec_out && conv_halo3_supports(d))) return GA_E_UNSUPPORTED;
         rc = conv_halo3_dispatch(k, stream, tile, vec_out, splits);

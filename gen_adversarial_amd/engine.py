@@ -26,7 +26,7 @@ from .e4e_spec import E4ESpec
 from .resnet_spec import ResNetSpec
 from .vgg_spec import VggSpec
 from .engine_core import (IMG_LD, RES_SCALE, TUNE_FILE, WS_FLOATS, Act, WeightStore, _ptr, conv_key,  # noqa: F401
-                          frag_ok, halo_ok, thin_ok, tune_cache)
+                          frag_ok, halo_ok, pw_ok, thin_ok, tune_cache)
 from .engine_classifiers import ClassifierBuilder
 from .engine_e4e import E4EBuilder
 from .engine_avae import AvaeBuilder
@@ -122,6 +122,7 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
         self._keep = []                      # weights etc.
         self._frag_ok = {}                   # id(ConvDesc) -> weight tensor of the convs that may run on tile 8
         self._thin_ok = {}                   # ... on tile 11
+        self._pw_ok = {}                     # ... on tile 12
         self.fwd = L.Plan()
         self.bwd = L.Plan()
         self._bwd_steps = []                 # closures emitting backward ops, replayed in reverse
@@ -150,7 +151,7 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
         self.share_encoder = bool(share_encoder) and rep > 1 and self.noise_eps == 0.0
         self.enc_rows = rows // rep if self.share_encoder else rows
         self.need_backward, self.image_s2d, self.cot_rep = need_backward, False, 1
-        self.bytes, self.acts, self.version, self._sampler_descs, self._keep, self._frag_ok, self._thin_ok = 0, {}, 0, [], [], {}, {}
+        self.bytes, self.acts, self.version, self._sampler_descs, self._keep, self._frag_ok, self._thin_ok, self._pw_ok = 0, {}, 0, [], [], {}, {}, {}
         self.fwd, self.bwd, self._bwd_steps, self._scratch = L.Plan(), L.Plan(), [], {}
         self.eps, self.purified, self.dpurified, self._purified_grad_nhwc = [], None, None, None
         return self
@@ -219,6 +220,9 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
             if (kh, kw, sn, sd, pad) == (3, 3, 1, 1, 1) and x2 is None and (cin or x.shape[3]) in (32, 64) and x.shape[1] % 8 == 0 \
                     and x.shape[2] % 16 == 0 and w.dim() == 2 and w.shape[1] == 9 * (cin or x.shape[3]):
                 self._thin_ok[id(d)] = w                    # tile 11 (conv_thin3): persistent weights-resident kernel, its own fragment order
+            if (kh, kw, sn, sd, pad) == (1, 1, 1, 1, 0) and x2 is None and (cin or x.shape[3]) % 16 == 0 \
+                    and w.numel() == (cout or y.shape[3]) * (cin or x.shape[3]):
+                self._pw_ok[id(d)] = w                      # tile 12 (conv_pw_frag): the one-tap fragment order, built lazily like tile 8's
         d.pro_scale, d.pro_shift, d.pro_act, d.pro_per_row = _ptr(pro_scale), _ptr(pro_shift), pro_act, pro_per_row
         No, Ho, Wo, Cy = y.shape
         d.y, d.ldy = _ptr(y), (ldy or Cy)
@@ -512,6 +516,8 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
                 tile, splits = 7, 1
             if tile in (5, 6, 7) and not halo_ok(d, tile, splits):
                 tile, splits = 0, 1
+            if tile == 12 and (splits > 1 or not (self._want_pw(d) and pw_ok(d, splits))):
+                tile, splits = 0, 1                 # (tile 12 gives the bits of tiles 1 - 4)
             d.tile, d.splits = int(tile), int(splits)
             d.ws, d.ws_floats = (_ptr(self.ws), WS_FLOATS) if splits > 1 else (None, 0)
         self.fwd.finalize()
@@ -533,6 +539,14 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
         d.w_frag = _ptr(self.store.frag_thin(w))
         return True
 
+    def _want_pw(self, d) -> bool:
+        """point d.w_frag at the one-tap fragment copy of a 1x1 conv's weights (built on first use); False when it cannot run on tile 12"""
+        w = self._pw_ok.get(id(d))
+        if w is None or self.dry_run:
+            return False
+        d.w_frag = _ptr(self.store.frag3(w.reshape(d.Cout, d.C1), taps=1))
+        return True
+
     def autotune(self, cache: Optional[dict] = None, reps: int = 3, save: Optional[str] = None, verbose: bool = False) -> dict:
         """time every (tile, split-K) candidate of every distinct conv shape on this GPU and keep the fastest."""
         if self.dry_run:
@@ -551,9 +565,10 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
             if halo and self._want_frag(d):
                 halo = halo + (8,)
             thin = (11,) if (d.w_hi and id(d) in self._thin_ok) else ()
-            for use_bf3, tile in [(m_, t_) for m_ in modes for t_ in (1, 2, 3, 4) + ((halo + thin) if m_ else ())]:
+            pw = (12,) if (d.w_hi and id(d) in self._pw_ok and d.C2 == 0 and (d.N * d.Ho * d.Wo) % 128 == 0) else ()
+            for use_bf3, tile in [(m_, t_) for m_ in modes for t_ in (1, 2, 3, 4) + ((halo + thin + pw) if m_ else ())]:
                 bm, bn = {1: (128, 128), 2: (128, 64), 3: (64, 64), 4: (128, 32), 5: (128, 128), 6: (128, 64), 7: (128, 32), 8: (128, 128),
-                          11: (128, 32)}[tile]
+                          11: (128, 32), 12: (128, 128)}[tile]
                 if bn >= 2 * max(32, d.Cout) and tile not in (4, 7):
                     continue
                 blocks = -(-M // bm) * -(-d.Cout // bn)
@@ -562,7 +577,7 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
                         continue
                     if tile >= 5 and splits > d.C1 // 32:          # the halo kernel splits K over 32-channel chunks
                         continue
-                    if tile == 11 and splits > 1:
+                    if tile in (11, 12) and splits > 1:
                         continue
                     t = L.ConvDesc.from_buffer_copy(d)
                     t.tile, t.splits = tile, splits
@@ -570,6 +585,8 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
                         t.w_frag = _ptr(self.store.frag_thin(self._thin_ok[id(d)]))
                     elif tile == 8:
                         t.w_frag = _ptr(self.store.frag3(self._frag_ok[id(d)]))
+                    elif tile == 12:
+                        t.w_frag = _ptr(self.store.frag3(self._pw_ok[id(d)].reshape(d.Cout, d.C1), taps=1))
                     if not use_bf3:
                         t.w_hi, t.w_lo = None, None
                     t.ws, t.ws_floats = (_ptr(self.ws), WS_FLOATS) if splits > 1 else (None, 0)

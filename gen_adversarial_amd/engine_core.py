@@ -39,8 +39,8 @@ def _ptr(t: Optional[torch.Tensor]):
 
 # ---- which explicit tile codes ga_conv2d takes for a descriptor (GA_E_UNSUPPORTED otherwise).  A restatement of the checks in
 #      csrc/conv_mfma.hip (ga_conv2d: the split-bf16 and vector-output preconditions), csrc/conv_bf3.hip (conv_bf3_supports),
-#      csrc/conv_halo3.hip (conv_halo3_supports, halo_geometry, launch_halo, launch_halo_bd) and csrc/conv_thin3.hip
-#      (conv_thin3_supports); tests/test_plan_convs_gpu.py checks that the library refuses exactly what these reject.
+#      csrc/conv_halo3.hip (conv_halo3_supports, halo_geometry, launch_halo, launch_halo_bd), csrc/conv_thin3.hip
+#      (conv_thin3_supports) and csrc/conv_pw_frag.hip (conv_pw_frag_supports); tests/test_plan_convs_gpu.py checks that the library refuses exactly what these reject.
 _HALO_HK, _HALO_LDH = 32, 40                # conv_halo3.hip: channels per chunk, bf16 per LDS pixel row
 _BF3_MODES = (0x000, 0x100, 0x001, 0x002, 0x003, 0x004, 0x010, 0x011, 0x020, 0x021)
 _HALO_MODES = (0x00, 0x01, 0x02, 0x03, 0x04, 0x10, 0x11, 0x20)
@@ -141,6 +141,23 @@ def thin_ok(d, splits: Optional[int] = None) -> bool:
     return d.Ho == d.Hi and d.Wo == d.Wi and d.Ho % 8 == 0 and d.Wo % 16 == 0 and d.Wo <= 255 * 16 and _pro_mode(d) in _HALO_MODES
 
 
+def pw_ok(d, splits: Optional[int] = None) -> bool:
+    """ga_conv2d runs d on tile 12 (conv_pw_frag_supports): the 1x1 kernel with its weight fragments read from d.w_frag (one tap;
+    without the copy the kernel gathers them from w_hi / w_lo, slower: the engine always builds it, _want_pw)"""
+    s = _splits(d, splits)
+    if s != 1 or not _a16(d.w_frag) or not _bf3_vec_out(d, s):
+        return False
+    if (d.KH, d.KW, d.sn, d.sd, d.pad, d.C2) != (1, 1, 1, 1, 0, 0) or d.Ho != d.Hi or d.Wo != d.Wi:
+        return False
+    if d.C1 % 16 or (d.N * d.Ho * d.Wo) % 128:
+        return False
+    # (a tensor past the loaders' 31-bit offsets is convolved in row sub-batches, whose pixel counts need not be whole tiles)
+    if d.N * d.Ho * d.Wo * max(d.ldx, d.ldy, d.ldadd, d.ldadd2, d.lddact) * 4 >= 0x7fffff00:
+        return False
+    mode = _pro_mode(d)
+    return mode in (0x00, 0x01, 0x10, 0x11) or (mode == 0x20 and (d.Ho * d.Wo) % 16 == 0)
+
+
 class WeightStore:
     """Folded weights on the device, shared by every engine (row count) built for one model."""
 
@@ -160,25 +177,29 @@ class WeightStore:
             self.bytes += 4 * w.numel()
         return self.splits[k][0], self.splits[k][1]
 
-    def frag3(self, w: torch.Tensor, m16: bool = False) -> torch.Tensor:
+    def frag3(self, w: torch.Tensor, m16: bool = False, taps: int = 9) -> torch.Tensor:
         """the split weights of a 3x3 conv ([Cout][9 * C] fp32, C % 32 == 0) in the MFMA-fragment order of ga_conv_desc.w_frag
-        (bf16 [ceil(Cout/128)][C/32][9][4 waves][2 k steps][hi | lo][64 lanes][8]); made once per tensor.
+        (bf16 [ceil(Cout/128)][C/32][taps][4 waves][2 k steps][hi | lo][64 lanes][8]); made once per tensor.
+        taps=1: the same order for a 1x1 conv ([Cout][C], tile 12 — forward weights and the transposed copies of the ^T launches
+        alike); C % 16 == 0, a last half group is zero-padded to 32 channels.
         m16: the order of the 16x16x32 fragments, [..][4 waves][2 halves of the wave's 32 channels][hi | lo][64 lanes][8], lane =
         16 * (k octet of the 32-deep chunk) + channel"""
-        k = ('frag3m16' if m16 else 'frag3', w.data_ptr())
+        k = (('frag3m16' if m16 else 'frag3') + ('' if taps == 9 else f'_taps{taps}'), w.data_ptr())
         if k not in self.splits:
             hi, lo = self.split(w)
             cout, kk = w.shape
-            c = kk // 9
-            nt, nkc = (cout + 127) // 128, c // 32
+            c = kk // taps
+            cp = (c + 31) // 32 * 32
+            assert kk == taps * c and (cp == c or (taps == 1 and c % 16 == 0)), (tuple(w.shape), taps)
+            nt, nkc = (cout + 127) // 128, cp // 32
 
             def arr(t):
-                tp = torch.zeros(nt * 128, kk, dtype=torch.bfloat16, device=t.device)
-                tp[:cout] = t
+                tp = torch.zeros(nt * 128, taps * cp, dtype=torch.bfloat16, device=t.device)
+                tp[:cout, :kk] = t
                 if m16:     # [nt, wave, half, channel, tap, chunk, k octet, e] -> [nt, chunk, tap, wave, half, k octet, channel, e]
-                    return tp.view(nt, 4, 2, 16, 9, nkc, 4, 8).permute(0, 5, 4, 1, 2, 6, 3, 7)
+                    return tp.view(nt, 4, 2, 16, taps, nkc, 4, 8).permute(0, 5, 4, 1, 2, 6, 3, 7)
                 # [nt, wave, row, tap, chunk, k step, lane half, e] -> [nt, chunk, tap, wave, k step, lane half, row, e]
-                return tp.view(nt, 4, 32, 9, nkc, 2, 2, 8).permute(0, 4, 3, 1, 5, 6, 2, 7)
+                return tp.view(nt, 4, 32, taps, nkc, 2, 2, 8).permute(0, 4, 3, 1, 5, 6, 2, 7)
             f = torch.stack([arr(hi), arr(lo)], dim=5).contiguous()          # hi | lo between the k step / half and the lane
             self.splits[k] = (f, w)
             self.bytes += 2 * f.numel()

@@ -87,7 +87,11 @@ typedef struct ga_conv_desc {
                                               GA_E_UNSUPPORTED otherwise); 8 = 128x128 on the same kernel with the weight
                                               fragments read from global memory (w_frag given, 128 % Wo == 0);
                                               11 = persistent weights-resident 3x3 for C1 == 32 or 64 on 8 x 16 pixel tiles (3x3, stride 1,
-                                              pad 1, Ho % 8 == 0, Wo % 16 == 0, no split-K, w_frag given in the tile-11 order below) */
+                                              pad 1, Ho % 8 == 0, Wo % 16 == 0, no split-K, w_frag given in the tile-11 order below);
+                                              12 = 128x128 for 1x1 / stride 1 / pad 0 with the weight fragments read from global memory (one
+                                              source, C1 % 16 == 0, N*Ho*Wo % 128 == 0, no split-K; GA_E_UNSUPPORTED otherwise; w_frag in the
+                                              tile-8 order with one tap, C1 zero-padded to a multiple of 32 — without it the kernel gathers
+                                              the same fragments from w_hi / w_lo, slower) */
     int splits;                            /* split-K factor (<=1: none); needs ws */
     float* ws;                             /* split-K workspace, >= splits*N*Ho*Wo*Cout floats, or NULL */
     long ws_floats;

@@ -28,6 +28,26 @@ if len(sys.argv) > 3 and sys.argv[3] == 'retune_thin':     # tile 11 (conv_thin3
     for d in eng._conv_descs():
         if id(d) in eng._thin_ok:
             start.pop(conv_key(d), None)
+old = None
+if len(sys.argv) > 3 and sys.argv[3] == 'retune_pw':       # tile 12 (conv_pw_frag) is new: time the 1x1 shapes it takes again
+    from gen_adversarial_amd.engine_core import conv_key, tune_cache
+    start = dict(tune_cache())
+    old = {}
+    for d in eng._conv_descs():                             # (several convs share a key)
+        if id(d) in eng._pw_ok and d.w_hi and d.C2 == 0 and (d.N * d.Ho * d.Wo) % 128 == 0 and conv_key(d) not in old:
+            old[conv_key(d)] = start.pop(conv_key(d), None)
 cache = eng.autotune(cache=start, reps=5, save=out, verbose=True)     # default: add missing shapes
+if old is not None:         # a shape changes its entry only where the new tile won: the other tiles were compared before
+    import json
+    for k, v in old.items():
+        print(f'retune_pw {k}: {v} -> {cache[k]}' + ('' if cache[k][0] == 12 else ' (kept)'), flush=True)
+        if cache[k][0] != 12:
+            if v is not None:
+                cache[k] = v
+            else:
+                del cache[k]
+    eng.apply_tuning(cache)
+    with open(out, 'w') as f:
+        json.dump(cache, f, indent=0, sort_keys=True)
 f1, fc1, _ = eng.fwd.time(s, iters=3, per_conv=True); b1, bc1, _ = eng.bwd.time(s, iters=3, per_conv=True)
 print(f'after : fwd {f1:.2f} (conv {fc1:.2f})  bwd {b1:.2f} (conv {bc1:.2f})  entries {len(cache)}')
