@@ -2,7 +2,7 @@
 //
 // On gfx950 the f32-input MFMA runs at the vector-ALU rate (64 FLOP/clk/SIMD); the bf16 MFMA runs 16x faster.  Every
 // fp32 operand x is split as x = hi + lo + r with hi = bf16(x), lo = bf16(x - hi), |r| <= 2^-16 |x|, and
-//     a*b  ~=  a_lo*b_hi + a_hi*b_lo + a_hi*b_hi        (three v_mfma_f32_32x32x16_bf16, fp32 accumulation)
+//     a*b  ~=  a_lo*b_hi + a_hi*b_lo + a_hi*b_hi        (three bf16 MFMAs, fp32 accumulation: mfma3 in conv_split.h)
 // which keeps ~16 mantissa bits per product (relative error ~2e-5 per product, averaging down over K) — two orders
 // of magnitude inside the path's 1e-3 parity bar — at 16/3 of the f32-MFMA rate.
 //   * activations: split in registers by the loader, after the prologue (affine / SiLU / ELU / ReLU), right before
@@ -12,19 +12,15 @@
 //   * LDS: four bf16 tiles per stage (A_hi, A_lo, B_hi, B_lo), rows of 32 k + 8 pad = 80 B: the 16-B fragment reads
 //     of a 16-lane group fall on 16 distinct slots of the 256-B bank row (80*r mod 256 is a bijection on r < 16);
 //   * fragments: lane (r = lane&31, h = lane>>5) reads the 8 bf16 A[r][8h..8h+7] / B[8h..8h+7][r] of a 16-deep k step
-//     as ONE ds_read_b128 — exactly the operand layout of v_mfma_f32_32x32x16_bf16;
+//     as ONE ds_read_b128 — exactly the operand layout of the 32x32x16 bf16 MFMA;
 //   * everything else (gather by buffer loads with per-row offsets and tap masks, scalar K cursor, register
 //     prefetch across the MFMAs, double-buffered LDS, LDS-transposed vector epilogue, split-K) is shared with the
 //     fp32 kernel.  Shapes this kernel does not take (stride-2 transposes, channel counts not multiple of 8, the
 //     3-channel image) run on the exact fp32-MFMA kernel.
-#include "ga_common.h"
+#include "conv_split.h"
 #include "conv_epilogue.h"
 
 namespace ga {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
 
 // -DGA_TRACE (make trace -> libga_ops_trace.so, tools/conv_trace.py): shader-clock stamps of the phases of each workgroup
 #ifdef GA_TRACE
@@ -62,12 +58,7 @@ conv_bf3_kernel(const ga_conv_desc d, const int tilesN, const int M, const int C
     __bf16* lds = reinterpret_cast<__bf16*>(smem);
 
     GA_STAMP(0)
-    int bid;
-    {
-        const int nb = gridDim.x, orig = blockIdx.x;
-        const int q = nb >> 3, r = nb & 7, xcd = orig & 7, k = orig >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    }
+    const int bid = xcd_tile_id();
     const int m0 = (bid / tilesN) * BM;
     const int n0 = (bid % tilesN) * BN;
 
@@ -187,31 +178,11 @@ conv_bf3_kernel(const ga_conv_desc d, const int tilesN, const int M, const int C
         for (int i = 0; i < RA; ++i) {
             floatx4 v = ra[set][i];
             if (AFF == 2) v = v * rs[set][i] + rt[set][i];
-            else if (AFF == 1) {
-                const floatx4 aff = v * rs[set][0] + rt[set][0];
-                if (d.flags & GA_CONV_PRO_PRELU) {          // uniform: nn.PReLU, the slopes travel in pro_scale
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * rs[set][0][e];
-                } else {
-                    v = aff;
-                }
-            }
-            if (ACT == GA_ACT_SILU) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = v[e] * fast_sigmoid(v[e]);
-            } else if (ACT == GA_ACT_ELU) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : __expf(v[e]) - 1.f;
-            } else if (ACT == GA_ACT_RELU) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-            } else if (ACT == GA_ACT_LRELU) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.01f * v[e];
-            }
+            else if (AFF == 1) v = pro_affine4(v, rs[set][0], rt[set][0], d.flags & GA_CONV_PRO_PRELU);
+            v = pro_act4<ACT>(v);
             if (AFF != 0) v = (okmask[set] >> i) & 1u ? v : zero;     // act(0) = 0 for all three: only a shift un-zeroes padding
-            const bf16x4 hi = __builtin_convertvector(v, bf16x4);
-            const bf16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, floatx4), bf16x4);
+            bf16x4 hi, lo;
+            split4(v, hi, lo);
             const int o = (r0 + 32 * i) * LDB + 4 * c4;
             *reinterpret_cast<bf16x4*>(Ah + o) = hi;
             *reinterpret_cast<bf16x4*>(Al + o) = lo;
@@ -271,11 +242,7 @@ conv_bf3_kernel(const ga_conv_desc d, const int tilesN, const int M, const int C
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-                }
+                for (int j = 0; j < TN; ++j) mfma3(acc[i][j], ah[i], al[i], bh[j], bl[j]);
         }
     };
 
@@ -331,15 +298,25 @@ static void launch_bf3_inst(const ga_conv_desc& d, hipStream_t stream, dim3 grid
                        fd_howo, fd_wo);
 }
 
-// (dual << 8) | (affine kind << 4) | activation — the key of the instantiated prologue variants
-static inline int conv_bf3_mode(const ga_conv_desc& d) {
-    return ((d.C2 > 0 ? 1 : 0) << 8) | ((d.pro_scale ? (d.pro_per_row ? 2 : 1) : 0) << 4) | d.pro_act;
-}
+// The instantiated prologue variants, X(mode, AFF, ACT, DUAL): the combinations the purification / classifier plans contain.
+// mode = (dual << 8) | conv_pro_mode
+#define GA_BF3_MODES(X)              \
+    X(0x000, 0, GA_ACT_NONE, false)  \
+    X(0x100, 0, GA_ACT_NONE, true)   \
+    X(0x001, 0, GA_ACT_SILU, false)  \
+    X(0x002, 0, GA_ACT_ELU, false)   \
+    X(0x003, 0, GA_ACT_RELU, false)  \
+    X(0x004, 0, GA_ACT_LRELU, false) \
+    X(0x010, 1, GA_ACT_NONE, false)  \
+    X(0x011, 1, GA_ACT_SILU, false)  \
+    X(0x020, 2, GA_ACT_NONE, false)  \
+    X(0x021, 2, GA_ACT_SILU, false)
+static inline int conv_bf3_mode(const ga_conv_desc& d) { return ((d.C2 > 0 ? 1 : 0) << 8) | conv_pro_mode(d); }
 
 // 1 when conv_bf3 has a kernel for this descriptor's prologue (ga_conv2d falls back to the fp32 kernel otherwise)
 int conv_bf3_supports(const ga_conv_desc& d) {
     switch (conv_bf3_mode(d)) {
-        case 0x000: case 0x100: case 0x001: case 0x002: case 0x003: case 0x004: case 0x010: case 0x011: case 0x020: case 0x021: return 1;
+        GA_BF3_MODES(GA_MODE_CASE) return 1;
         default: return 0;
     }
 }
@@ -356,18 +333,10 @@ static int launch_bf3(const ga_conv_desc& d, hipStream_t stream, int vec_out, in
     const size_t lds_c = (size_t)BM * (BN + 4) * sizeof(float);
     if (lds_c > lds) lds = lds_c;
     const dim3 grid(tilesM * tilesN, splits);
-#define GA_BF3(A, C, D) launch_bf3_inst<WM, WN, TM, TN, A, C, D>(d, stream, grid, lds, tilesN, M, Ctot, Ktot, nkc, vec_out)
-    switch (conv_bf3_mode(d)) {         // the prologue combinations the purification / classifier plans contain
-        case 0x000: GA_BF3(0, GA_ACT_NONE, false); break;
-        case 0x100: GA_BF3(0, GA_ACT_NONE, true); break;
-        case 0x001: GA_BF3(0, GA_ACT_SILU, false); break;
-        case 0x002: GA_BF3(0, GA_ACT_ELU, false); break;
-        case 0x003: GA_BF3(0, GA_ACT_RELU, false); break;
-        case 0x004: GA_BF3(0, GA_ACT_LRELU, false); break;
-        case 0x010: GA_BF3(1, GA_ACT_NONE, false); break;
-        case 0x011: GA_BF3(1, GA_ACT_SILU, false); break;
-        case 0x020: GA_BF3(2, GA_ACT_NONE, false); break;
-        case 0x021: GA_BF3(2, GA_ACT_SILU, false); break;
+#define GA_BF3(MODE, A, C, D) \
+    case MODE: launch_bf3_inst<WM, WN, TM, TN, A, C, D>(d, stream, grid, lds, tilesN, M, Ctot, Ktot, nkc, vec_out); break;
+    switch (conv_bf3_mode(d)) {
+        GA_BF3_MODES(GA_BF3)
         default: return GA_E_UNSUPPORTED;
     }
 #undef GA_BF3

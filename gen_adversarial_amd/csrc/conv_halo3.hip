@@ -14,14 +14,10 @@
 // tile is a 128-pixel SEGMENT of one row and its window 3 x 130 pixels (3x the tile instead of 9x); 13 patch slots per thread
 // instead of 9, hence a second set of instantiations (template parameter RP).
 #include <type_traits>
-#include "ga_common.h"
+#include "conv_split.h"
 #include "conv_epilogue.h"
 
 namespace ga {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
 
 #ifdef GA_TRACE     // see conv_bf3.hip: per-workgroup phase stamps for tools/conv_trace.py
 __device__ unsigned long long ga_trace_buf_halo[8 * 8192];
@@ -70,12 +66,7 @@ conv_halo3_kernel(const ga_conv_desc d, const int tilesN, const int M, const int
     __bf16* Bst = Pl + g.NI * g.IS;                         // two weight stages
 
     GA_HSTAMP(0)
-    int bid;
-    {
-        const int nb = gridDim.x, orig = blockIdx.x;
-        const int q = nb >> 3, r = nb & 7, xcd = orig & 7, k = orig >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    }
+    const int bid = xcd_tile_id();
     const int m0 = (bid / tilesN) * BM;
     const int n0 = (bid % tilesN) * BN;
 
@@ -154,36 +145,17 @@ conv_halo3_kernel(const ga_conv_desc d, const int tilesN, const int M, const int
         for (int j = 0; j < RPMAX; ++j) {
             if (j < rp) {
                 floatx4 v = rpat[j];
-                if (AFF == 1) {
-                    if (d.flags & GA_CONV_PRO_PRELU) {      // uniform: nn.PReLU, the slopes travel in pro_scale
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * rs[e];
-                    } else {
-                        v = v * rs + rt;
-                    }
-                }
+                if (AFF == 1) v = pro_affine4(v, rs, rt, d.flags & GA_CONV_PRO_PRELU);
                 if (AFF == 2) {     // per-(image, channel) scale / shift: small and L2-resident, fetched as the slot is converted
                     const int prow = min(n_first + (int)((pmeta[j] >> 20) & 15u), d.N - 1) * C + 4 * c4 + cur_chunk * HK;
                     const floatx4 ps = *reinterpret_cast<const floatx4*>(d.pro_scale + prow);
                     const floatx4 pt = *reinterpret_cast<const floatx4*>(d.pro_shift + prow);
                     v = v * ps + pt;
                 }
-                if (ACT == GA_ACT_SILU) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = v[e] * fast_sigmoid(v[e]);
-                } else if (ACT == GA_ACT_ELU) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : __expf(v[e]) - 1.f;
-                } else if (ACT == GA_ACT_RELU) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-                } else if (ACT == GA_ACT_LRELU) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.01f * v[e];
-                }
+                v = pro_act4<ACT>(v);
                 if (AFF != 0) v = pbase[j] != INV ? v : zero;           // only a shift un-zeroes the padding
-                const bf16x4 hi = __builtin_convertvector(v, bf16x4);
-                const bf16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, floatx4), bf16x4);
+                bf16x4 hi, lo;
+                split4(v, hi, lo);
                 if (!(pmeta[j] & (1u << 30))) {
                     *reinterpret_cast<bf16x4*>(Ph + (pmeta[j] & 0xfffffu)) = hi;
                     *reinterpret_cast<bf16x4*>(Pl + (pmeta[j] & 0xfffffu)) = lo;
@@ -243,11 +215,7 @@ conv_halo3_kernel(const ga_conv_desc d, const int tilesN, const int M, const int
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-                }
+                for (int j = 0; j < TN; ++j) mfma3(acc[i][j], ah[i], al[i], bh[j], bl[j]);
         }
     };
 
@@ -338,7 +306,7 @@ static void launch_halo_inst(const ga_conv_desc& d, hipStream_t stream, dim3 gri
 // barrier.  They are loaded a whole step ahead with fully coalesced 1-KB wave loads from a copy of the weights laid out in
 // fragment order at load time (`w_frag`: [N tile][chunk][tap][wave][k step][hi | lo][lane][8 bf16], written by the host once),
 // and the patch is double-buffered where it fits: ONE barrier per 32-channel chunk (9 taps, 216 MFMAs per wave) instead of nine.
-// Same operand split, k order and accumulation order as conv_halo3_kernel: bitwise the same results.
+// Same operand split and accumulation order (conv_split.h: split4, mfma3) and k order as conv_halo3_kernel: bitwise the same results.
 // ---------------------------------------------------------------------------------------------------------------------
 template <int AFF, int ACT, int RPMAX, bool M16>
 __global__ void __launch_bounds__(256, 2)
@@ -350,13 +318,7 @@ conv_halo3_bd_kernel(const ga_conv_desc d, const int tilesN, const int M, const 
     const int plane = g.NI * g.IS;                           // bf16 elements of one patch plane (hi or lo)
     __bf16* Pbase = reinterpret_cast<__bf16*>(smem);         // buffer b: hi at b * 2 * plane, lo behind it
     GA_HSTAMP(0)
-
-    int bid;
-    {
-        const int nb = gridDim.x, orig = blockIdx.x;
-        const int q = nb >> 3, r = nb & 7, xcd = orig & 7, k = orig >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    }
+    const int bid = xcd_tile_id();
     const int m0 = (bid / tilesN) * BM;
     const int nt = bid % tilesN, n0 = nt * BN;
 
@@ -460,35 +422,16 @@ conv_halo3_bd_kernel(const ga_conv_desc d, const int tilesN, const int M, const 
             if (j < rp) {
                 floatx4 v = rpat[j];
                 const int pl = sl_p[j * 256 + tid];
-                if (AFF == 1) {
-                    if (d.flags & GA_CONV_PRO_PRELU) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * rs[e];
-                    } else {
-                        v = v * rs + rt;
-                    }
-                }
+                if (AFF == 1) v = pro_affine4(v, rs, rt, d.flags & GA_CONV_PRO_PRELU);
                 if (AFF == 2) {
                     const int img = pl != 0xffff ? fd_div(4 * pl, g.fd_is) : 0;        // (no such patch pixel: any table row, the value is dropped)
                     const float* tp = ptab + img * C + chunk * HK + 4 * c4;
                     v = v * *reinterpret_cast<const floatx4*>(tp) + *reinterpret_cast<const floatx4*>(tp + TI * C);
                 }
-                if (ACT == GA_ACT_SILU) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = v[e] * fast_sigmoid(v[e]);
-                } else if (ACT == GA_ACT_ELU) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : __expf(v[e]) - 1.f;
-                } else if (ACT == GA_ACT_RELU) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-                } else if (ACT == GA_ACT_LRELU) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.01f * v[e];
-                }
+                v = pro_act4<ACT>(v);
                 if (AFF != 0) v = sl_g[j * 256 + tid] != INV ? v : zero;        // only a shift un-zeroes the padding
-                const bf16x4 hi = __builtin_convertvector(v, bf16x4);
-                const bf16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, floatx4), bf16x4);
+                bf16x4 hi, lo;
+                split4(v, hi, lo);
                 if (pl != 0xffff) {
                     *reinterpret_cast<bf16x4*>(Ph + 4 * pl) = hi;
                     *reinterpret_cast<bf16x4*>(Pl + 4 * pl) = lo;
@@ -557,11 +500,7 @@ conv_halo3_bd_kernel(const ga_conv_desc d, const int tilesN, const int M, const 
         } else {
             const bf16x8 bh = __builtin_bit_cast(bf16x8, b[2 * sel]), bl = __builtin_bit_cast(bf16x8, b[2 * sel + 1]);
 #pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(als[set][i], bh, acc[i][0], 0, 0, 0);
-                acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahs[set][i], bl, acc[i][0], 0, 0, 0);
-                acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahs[set][i], bh, acc[i][0], 0, 0, 0);
-            }
+            for (int i = 0; i < TM; ++i) mfma3(acc[i][0], ahs[set][i], als[set][i], bh, bl);
         }
     };
 
@@ -682,10 +621,6 @@ static void launch_halo_bd_inst(const ga_conv_desc& d, hipStream_t stream, dim3 
                        tab_off);
 }
 
-static inline int halo_mode(const ga_conv_desc& d) {
-    return ((d.pro_scale ? (d.pro_per_row ? 2 : 1) : 0) << 4) | d.pro_act;
-}
-
 // 1 when the descriptor is a 3x3 / stride 1 / pad 1 single-source convolution whose 128-pixel tiles are whole image rows
 // (or whole small images) or 128-pixel segments of one row
 int conv_halo3_supports(const ga_conv_desc& d) {
@@ -695,10 +630,7 @@ int conv_halo3_supports(const ga_conv_desc& d) {
     const bool rows = d.Wo < 128 && 128 % d.Wo == 0 && (HoWo % 128 == 0 || 128 % HoWo == 0);   // tiles of whole rows / images
     const bool segs = d.Wo % 128 == 0;                                                          // tiles = row segments
     if (!rows && !segs) return 0;
-    switch (halo_mode(d)) {
-        case 0x00: case 0x01: case 0x02: case 0x03: case 0x04: case 0x10: case 0x11: case 0x20: return 1;
-        default: return 0;
-    }
+    return conv3_mode_supported(d);
 }
 
 static int halo_geometry(const ga_conv_desc& d, const int BM, halo_geom& g, const int ldh = LDH) {
@@ -742,25 +674,18 @@ static int launch_halo(const ga_conv_desc& d, hipStream_t stream, int vec_out, i
     const size_t lds_c = (size_t)BM * (BN + 4) * sizeof(float);
     if (lds_c > lds) lds = lds_c;
     const dim3 grid(tilesM * tilesN, splits);
-    // row-segment tiles (13 patch slots) are instantiated for the prologues the wide layers use: none (backward convs), the
-    // per-channel affine / PReLU (e4e IR units at 256^2 and 128^2) and the per-row style scale (StyleGAN2 modulated convs)
-#define GA_HALO(A, C) launch_halo_inst<WM, WN, TM, TN, A, C, 9>(d, stream, grid, lds, tilesN, M, Ktot, nkc, vec_out, g)
-#define GA_HALO_W(A, C)                                                                                               \
-    if (g.P > 9 * 32) launch_halo_inst<WM, WN, TM, TN, A, C, 13>(d, stream, grid, lds, tilesN, M, Ktot, nkc, vec_out, g);  \
-    else GA_HALO(A, C)
-    if (g.P > 9 * 32 && !(halo_mode(d) == 0x00 || halo_mode(d) == 0x10 || halo_mode(d) == 0x20)) return GA_E_UNSUPPORTED;
-    switch (halo_mode(d)) {
-        case 0x00: GA_HALO_W(0, GA_ACT_NONE); break;
-        case 0x01: GA_HALO(0, GA_ACT_SILU); break;
-        case 0x02: GA_HALO(0, GA_ACT_ELU); break;
-        case 0x03: GA_HALO(0, GA_ACT_RELU); break;
-        case 0x04: GA_HALO(0, GA_ACT_LRELU); break;
-        case 0x10: GA_HALO_W(1, GA_ACT_NONE); break;
-        case 0x11: GA_HALO(0 + 1, GA_ACT_SILU); break;
-        case 0x20: GA_HALO_W(2, GA_ACT_NONE); break;
+    // row-segment tiles (13 patch slots) exist for the WIDE entries of the list only
+    const bool wide = g.P > 9 * 32;
+#define GA_HALO(MODE, A, C, WIDE)                                                                                                    \
+    case MODE:                                                                                                                       \
+        if (!wide) launch_halo_inst<WM, WN, TM, TN, A, C, 9>(d, stream, grid, lds, tilesN, M, Ktot, nkc, vec_out, g);                \
+        else if constexpr (WIDE) launch_halo_inst<WM, WN, TM, TN, A, C, 13>(d, stream, grid, lds, tilesN, M, Ktot, nkc, vec_out, g); \
+        else return GA_E_UNSUPPORTED;                                                                                                \
+        break;
+    switch (conv_pro_mode(d)) {
+        GA_CONV3_MODES(GA_HALO)
         default: return GA_E_UNSUPPORTED;
     }
-#undef GA_HALO_W
 #undef GA_HALO
     return check_launch();
 }
@@ -776,7 +701,7 @@ static int launch_halo_bd(const ga_conv_desc& d, hipStream_t stream, int vec_out
     if (splits > nkc) return GA_E_UNSUPPORTED;
     const int tilesM = (M + BM - 1) / BM, tilesN = (d.Cout + BN - 1) / BN;
     const size_t patch = (size_t)2 * g.NI * g.IS * 2;                   // hi + lo planes of one buffer, bytes
-    const int mode = halo_mode(d);
+    const int mode = conv_pro_mode(d);
     const int rp = (g.P * 8 + 255) >> 8;                                // patch slots per thread
     const size_t tab = (size_t)rp * 256 * 6                             // slot tables: global offsets (int) + LDS offsets (short)
                        + (mode >= 0x10 ? (size_t)2 * (mode == 0x20 ? g.NI : 1) * d.C1 * sizeof(float) : 0);      // prologue table
@@ -790,27 +715,17 @@ static int launch_halo_bd(const ga_conv_desc& d, hipStream_t stream, int vec_out
     // the other stream's kernel — out of phase, so that one's setup / epilogue would overlap the other's K loop: 5,579 against 5,949 -
     // 5,967 rows/s on the same box, gpurun_out/r04_ab_epi.log: a lone conv launch then runs at half occupancy)
     const dim3 grid(tilesM * tilesN, splits);
-#define GA_HBD(A, C) launch_halo_bd_inst<A, C, 9, M16>(d, stream, grid, lds, tilesN, M, nkc, vec_out, g, dbuf, tab_off)
     if (g.P > 9 * 32) return GA_E_UNSUPPORTED;                          // row-segment tiles of wide images: the LDS-staged kernel
+#define GA_HBD(MODE, A, C, WIDE) \
+    case MODE: launch_halo_bd_inst<A, C, 9, M16>(d, stream, grid, lds, tilesN, M, nkc, vec_out, g, dbuf, tab_off); break;
+    switch (mode) {
 #ifdef GA_HALO_EXP_ONLY     // quick experiment builds (make hexp): two prologues only
-    switch (halo_mode(d)) {
-        case 0x00: GA_HBD(0, GA_ACT_NONE); break;
-        case 0x01: GA_HBD(0, GA_ACT_SILU); break;
-        default: return GA_E_UNSUPPORTED;
-    }
+        GA_CONV3_MODES_EXP(GA_HBD)
 #else
-    switch (halo_mode(d)) {
-        case 0x00: GA_HBD(0, GA_ACT_NONE); break;
-        case 0x01: GA_HBD(0, GA_ACT_SILU); break;
-        case 0x02: GA_HBD(0, GA_ACT_ELU); break;
-        case 0x03: GA_HBD(0, GA_ACT_RELU); break;
-        case 0x04: GA_HBD(0, GA_ACT_LRELU); break;
-        case 0x10: GA_HBD(1, GA_ACT_NONE); break;
-        case 0x11: GA_HBD(1, GA_ACT_SILU); break;
-        case 0x20: GA_HBD(2, GA_ACT_NONE); break;
+        GA_CONV3_MODES(GA_HBD)
+#endif
         default: return GA_E_UNSUPPORTED;
     }
-#endif
 #undef GA_HBD
     return check_launch();
 }

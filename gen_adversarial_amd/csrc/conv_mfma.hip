@@ -18,7 +18,7 @@
 //   * Split-K (small M x Cout with a long K: samplers, the classifier head): grid.y = splits, raw partial tiles go to
 //     a caller-provided workspace and a second kernel sums them in a fixed order and applies the epilogue.
 //   * blockIdx is remapped so that consecutive logical tiles (which share the A panel) run on one XCD's L2.
-#include "ga_common.h"
+#include "conv_split.h"
 #include "conv_epilogue.h"
 
 namespace ga {
@@ -44,12 +44,7 @@ conv_mfma_kernel(const ga_conv_desc d, const int tilesN, const int M, const int 
 
     // ---- XCD-aware tile order: blocks b, b+8, b+16.. share an XCD (round-robin dispatch); give each XCD a
     //      contiguous range of logical tiles.  Bijective for any grid size.
-    int bid;
-    {
-        const int nb = gridDim.x, orig = blockIdx.x;
-        const int q = nb >> 3, r = nb & 7, xcd = orig & 7, k = orig >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    }
+    const int bid = xcd_tile_id();
     const int m0 = (bid / tilesN) * BM;
     const int n0 = (bid % tilesN) * BN;
 

@@ -13,16 +13,12 @@
 //     and in `w_frag`);
 //   * one fragment register set, refilled tile by tile: the two ds_read_b128 of M tile i for the next k step follow the three MFMAs
 //     that consumed them (9 MFMAs before their next use).
-// Per output element the products are summed chunk-major, k ascending, lo*hi, hi*lo, hi*hi — the order of conv_bf3: results are
-// bitwise those of tiles 1 - 4.  No split-K, one source, pixel counts that are multiples of 128.
-#include "ga_common.h"
+// Per output element the products are summed chunk-major, k ascending, each through mfma3 (conv_split.h) — the order of conv_bf3:
+// results are bitwise those of tiles 1 - 4.  No split-K, one source, pixel counts that are multiples of 128.
+#include "conv_split.h"
 #include "conv_epilogue.h"
 
 namespace ga {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
 
 constexpr int PK = 128;         // channels per chunk
 constexpr int PLD = PK + 8;     // bf16 per LDS pixel row: 272 B, the 16 rows of a ds_read_b128 lane group fall on 16 distinct 16-B slots
@@ -36,12 +32,7 @@ conv_pw_frag_kernel(const ga_conv_desc d, const int tilesN, const int M, const i
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __bf16* Ph = reinterpret_cast<__bf16*>(smem);           // [128 pixels][PLD] hi, then lo
 
-    int bid;
-    {
-        const int nb = gridDim.x, orig = blockIdx.x;
-        const int q = nb >> 3, r = nb & 7, xcd = orig & 7, k = orig >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    }
+    const int bid = xcd_tile_id();
     const int m0 = (bid / tilesN) * BM;
     const int nt = bid % tilesN, n0 = nt * BN;
 
@@ -77,19 +68,12 @@ conv_pw_frag_kernel(const ga_conv_desc d, const int tilesN, const int M, const i
 #pragma unroll
         for (int j = 0; j < PSL; ++j) {
             floatx4 v = rpat[j];
-            if (AFF == 1 && (d.flags & GA_CONV_PRO_PRELU)) {        // uniform: nn.PReLU, the slopes travel in pro_scale
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * rs[e];
-            } else if (AFF != 0) {
-                v = v * rs + rt;
-            }
-            if (ACT == GA_ACT_SILU) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = v[e] * fast_sigmoid(v[e]);
-            }
+            if (AFF == 1) v = pro_affine4(v, rs, rt, d.flags & GA_CONV_PRO_PRELU);
+            if (AFF == 2) v = v * rs + rt;
+            v = pro_act4<ACT>(v);
             if (AFF != 0) v = sval ? v : zero;              // only a shift un-zeroes the padding
-            const bf16x4 hi = __builtin_convertvector(v, bf16x4);
-            const bf16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, floatx4), bf16x4);
+            bf16x4 hi, lo;
+            split4(v, hi, lo);
             *reinterpret_cast<bf16x4*>(Sh + j * PLD) = hi;
             *reinterpret_cast<bf16x4*>(Sh + BM * PLD + j * PLD) = lo;
         }
@@ -141,9 +125,7 @@ conv_pw_frag_kernel(const ga_conv_desc d, const int tilesN, const int M, const i
             const bf16x8 bh = __builtin_bit_cast(bf16x8, bcur[2 * ks]), bl = __builtin_bit_cast(bf16x8, bcur[2 * ks + 1]);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh, acc[i][0], 0, 0, 0);
-                acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl, acc[i][0], 0, 0, 0);
-                acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh, acc[i][0], 0, 0, 0);
+                mfma3(acc[i][0], ah[i], al[i], bh, bl);
                 if (ks == 0 || more) load_A(a, i, (ks + 1) * 16);
             }
 #pragma unroll
@@ -202,9 +184,15 @@ static void launch_pw_frag_inst(const ga_conv_desc& d, hipStream_t stream, dim3 
                        make_fastdiv(d.Ho * d.Wo));
 }
 
-static inline int pw_frag_mode(const ga_conv_desc& d) {
-    return ((d.pro_scale ? (d.pro_per_row ? 2 : 1) : 0) << 4) | d.pro_act;
-}
+// The instantiated prologue variants, X(mode, AFF, ACT): what the decoder / encoder 1x1 layers use.  The quick experiment builds
+// (GA_PWF_EXP_ONLY) instantiate the first only.
+#define GA_PWF_MODES_EXP(X) X(0x00, 0, GA_ACT_NONE)
+#define GA_PWF_MODES(X)      \
+    GA_PWF_MODES_EXP(X)      \
+    X(0x01, 0, GA_ACT_SILU)  \
+    X(0x10, 1, GA_ACT_NONE)  \
+    X(0x11, 1, GA_ACT_SILU)  \
+    X(0x20, 2, GA_ACT_NONE)
 
 // 1 when tile code 12 takes the descriptor: 1x1 / stride 1 / pad 0, one source whose channel count is a multiple of the MFMA k step,
 // whole 128-pixel tiles, no split-K, the fragment-ordered weight copy aligned when given, a prologue the decoder / encoder 1x1 layers use (a per-row
@@ -214,9 +202,9 @@ int conv_pw_frag_supports(const ga_conv_desc& d, const int splits) {
     if (d.Ho != d.Hi || d.Wo != d.Wi || d.C1 % 16 != 0 || splits != 1) return 0;
     if (((long)d.N * d.Ho * d.Wo) % 128 != 0) return 0;
     if (d.w_frag && !aligned16(d.w_frag)) return 0;
-    switch (pw_frag_mode(d)) {
-        case 0x00: case 0x01: case 0x10: case 0x11: return 1;
-        case 0x20: return (d.Ho * d.Wo) % PSL == 0;
+    const int mode = conv_pro_mode(d);
+    switch (mode) {
+        GA_PWF_MODES(GA_MODE_CASE) return mode != 0x20 || (d.Ho * d.Wo) % PSL == 0;
         default: return 0;
     }
 }
@@ -231,14 +219,12 @@ int conv_pw_frag_dispatch(const ga_conv_desc& d, hipStream_t stream, int vec_out
     const size_t lds_c = (size_t)BM * (BN + 4) * sizeof(float);
     if (lds_c > lds) lds = lds_c;
     const dim3 grid(tilesM * tilesN, 1);
-#define GA_PWF(A, C) launch_pw_frag_inst<A, C>(d, stream, grid, lds, tilesN, M, nk32, vec_out)
-    switch (pw_frag_mode(d)) {
-        case 0x00: GA_PWF(0, GA_ACT_NONE); break;
-#ifndef GA_PWF_EXP_ONLY     // (quick experiment builds: one instantiation)
-        case 0x01: GA_PWF(0, GA_ACT_SILU); break;
-        case 0x10: GA_PWF(1, GA_ACT_NONE); break;
-        case 0x11: GA_PWF(1, GA_ACT_SILU); break;
-        case 0x20: GA_PWF(2, GA_ACT_NONE); break;
+#define GA_PWF(MODE, A, C) case MODE: launch_pw_frag_inst<A, C>(d, stream, grid, lds, tilesN, M, nk32, vec_out); break;
+    switch (conv_pro_mode(d)) {
+#ifdef GA_PWF_EXP_ONLY
+        GA_PWF_MODES_EXP(GA_PWF)
+#else
+        GA_PWF_MODES(GA_PWF)
 #endif
         default: return GA_E_UNSUPPORTED;
     }

@@ -11,18 +11,15 @@
 //   * requests tile t+1's window from memory before the MFMAs and the epilogue of tile t.
 // Per tile: prologue + bf16 split of the window into LDS | barrier | 9 taps x 2 k steps x 3 MFMAs, A and B fragments both from LDS at
 // immediate offsets | barrier | conv_epilogue through the window's LDS (bias, act', addends; 2-D row map) | barrier.
-// Same operand split, k order and MFMA order as conv_halo3 (tap-major inside the chunk): results are BITWISE those of tile 7.
+// Same operand split and MFMA order (conv_split.h: split4, mfma3) and k order as conv_halo3 (tap-major inside the chunk): results are
+// BITWISE those of tile 7.
 // Cout > 32: grid.y output-channel tiles, each staging the window itself (the layers this is for have Cout <= 32, or few tiles).
 // 64 input channels (template parameter CIN): four k steps per tap (108 MFMAs per wave and tile), 74 KB of weight fragments and a
 // 55 KB window: ONE workgroup per CU; the next window's 12 loads per thread are in flight under the MFMAs and the epilogue.
-#include "ga_common.h"
+#include "conv_split.h"
 #include "conv_epilogue.h"
 
 namespace ga {
-
-typedef __bf16 tk_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 tk_bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned tk_uintx4 __attribute__((ext_vector_type(4)));
 
 constexpr int TK_TH = 8, TK_TW = 16;        // tile: 8 rows x 16 columns = 128 output pixels
 constexpr int TK_PH = TK_TH + 2, TK_PW = TK_TW + 2, TK_P = TK_PH * TK_PW;      // window: 10 x 18 = 180 pixels
@@ -63,9 +60,9 @@ conv_thin3_kernel(const ga_conv_desc d, const thin_geom g, const int M) {
 
     // ---- once per workgroup: the weight fragments of this output-channel tile -> LDS (lane-linear 1-KB pieces: conflict-free reads)
     {
-        const tk_uintx4* wf = reinterpret_cast<const tk_uintx4*>(d.w_frag) + (size_t)nt * (TK_BFR / 8);
+        const uintx4* wf = reinterpret_cast<const uintx4*>(d.w_frag) + (size_t)nt * (TK_BFR / 8);
 #pragma unroll
-        for (int i = 0; i < TK_BFR / 8 / 256; ++i) reinterpret_cast<tk_uintx4*>(Bs)[tid + 256 * i] = wf[tid + 256 * i];
+        for (int i = 0; i < TK_BFR / 8 / 256; ++i) reinterpret_cast<uintx4*>(Bs)[tid + 256 * i] = wf[tid + 256 * i];
     }
     // window slot j of this thread: window pixel (tid + 256 j) / Q = (py, px), channel quad c4
     int slot_yx[TK_SLOTS], slot_lds[TK_SLOTS];
@@ -118,34 +115,15 @@ conv_thin3_kernel(const ga_conv_desc d, const thin_geom g, const int M) {
 #pragma unroll
         for (int j = 0; j < TK_SLOTS; ++j) {
             floatx4 v = rpat[j];
-            if (AFF == 1) {
-                if (d.flags & GA_CONV_PRO_PRELU) {          // uniform: nn.PReLU, the slopes travel in pro_scale
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * rs[e];
-                } else {
-                    v = v * rs + rt;
-                }
-            }
+            if (AFF == 1) v = pro_affine4(v, rs, rt, d.flags & GA_CONV_PRO_PRELU);
             if (AFF == 2) v = v * ps + pt;
-            if (ACT == GA_ACT_SILU) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = v[e] * fast_sigmoid(v[e]);
-            } else if (ACT == GA_ACT_ELU) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : __expf(v[e]) - 1.f;
-            } else if (ACT == GA_ACT_RELU) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-            } else if (ACT == GA_ACT_LRELU) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.01f * v[e];
-            }
+            v = pro_act4<ACT>(v);
             if (AFF != 0) v = (okmask >> j) & 1u ? v : zero;            // only a shift un-zeroes the padding
-            const tk_bf16x4 hi = __builtin_convertvector(v, tk_bf16x4);
-            const tk_bf16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, floatx4), tk_bf16x4);
+            bf16x4 hi, lo;
+            split4(v, hi, lo);
             if (slot_yx[j] >= 0) {
-                *reinterpret_cast<tk_bf16x4*>(Ph + slot_lds[j]) = hi;
-                *reinterpret_cast<tk_bf16x4*>(Pl + slot_lds[j]) = lo;
+                *reinterpret_cast<bf16x4*>(Ph + slot_lds[j]) = hi;
+                *reinterpret_cast<bf16x4*>(Pl + slot_lds[j]) = lo;
             }
         }
     };
@@ -167,13 +145,11 @@ conv_thin3_kernel(const ga_conv_desc d, const thin_geom g, const int M) {
 #pragma unroll
                 for (int k2 = 0; k2 < 2; ++k2) {
                     const int ks = 2 * ch + k2;
-                    const tk_bf16x8 ah = *reinterpret_cast<const tk_bf16x8*>(fa_h + tapoff + ks * 16);
-                    const tk_bf16x8 al = *reinterpret_cast<const tk_bf16x8*>(fa_l + tapoff + ks * 16);
-                    const tk_bf16x8 bh = *reinterpret_cast<const tk_bf16x8*>(fb + ((tap * KS + ks) * 2 + 0) * 512);
-                    const tk_bf16x8 bl = *reinterpret_cast<const tk_bf16x8*>(fb + ((tap * KS + ks) * 2 + 1) * 512);
-                    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[0][0], 0, 0, 0);
-                    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[0][0], 0, 0, 0);
-                    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[0][0], 0, 0, 0);
+                    const bf16x8 ah = *reinterpret_cast<const bf16x8*>(fa_h + tapoff + ks * 16);
+                    const bf16x8 al = *reinterpret_cast<const bf16x8*>(fa_l + tapoff + ks * 16);
+                    const bf16x8 bh = *reinterpret_cast<const bf16x8*>(fb + ((tap * KS + ks) * 2 + 0) * 512);
+                    const bf16x8 bl = *reinterpret_cast<const bf16x8*>(fb + ((tap * KS + ks) * 2 + 1) * 512);
+                    mfma3(acc[0][0], ah, al, bh, bl);
                 }
             }
         }
@@ -194,32 +170,18 @@ static void launch_thin_inst(const ga_conv_desc& d, hipStream_t stream, dim3 gri
     hipLaunchKernelGGL((conv_thin3_kernel<CIN, AFF, ACT>), grid, dim3(256), lds, stream, d, g, M);
 }
 
-static inline int thin_mode(const ga_conv_desc& d) {
-    return ((d.pro_scale ? (d.pro_per_row ? 2 : 1) : 0) << 4) | d.pro_act;
-}
-
 // 1 when tile code 11 takes the descriptor: 3x3 / stride 1 / pad 1, one source of exactly 32 or 64 channels, images of 8 x 16 tiles
 int conv_thin3_supports(const ga_conv_desc& d) {
     if (d.KH != 3 || d.KW != 3 || d.sn != 1 || d.sd != 1 || d.pad != 1 || d.C2 != 0 || (d.C1 != 32 && d.C1 != 64)) return 0;
     if (d.Ho != d.Hi || d.Wo != d.Wi || d.Ho % TK_TH || d.Wo % TK_TW || d.Wo > 255 * TK_TW) return 0;
-    switch (thin_mode(d)) {
-        case 0x00: case 0x01: case 0x02: case 0x03: case 0x04: case 0x10: case 0x11: case 0x20: return 1;
-        default: return 0;
-    }
+    return conv3_mode_supported(d);
 }
 
 template <int CIN>
 static int thin_dispatch_c(const ga_conv_desc& d, hipStream_t stream, dim3 grid, const thin_geom& g, int M) {
-#define GA_THIN(A, C) launch_thin_inst<CIN, A, C>(d, stream, grid, g, M)
-    switch (thin_mode(d)) {
-        case 0x00: GA_THIN(0, GA_ACT_NONE); break;
-        case 0x01: GA_THIN(0, GA_ACT_SILU); break;
-        case 0x02: GA_THIN(0, GA_ACT_ELU); break;
-        case 0x03: GA_THIN(0, GA_ACT_RELU); break;
-        case 0x04: GA_THIN(0, GA_ACT_LRELU); break;
-        case 0x10: GA_THIN(1, GA_ACT_NONE); break;
-        case 0x11: GA_THIN(1, GA_ACT_SILU); break;
-        case 0x20: GA_THIN(2, GA_ACT_NONE); break;
+#define GA_THIN(MODE, A, C, WIDE) case MODE: launch_thin_inst<CIN, A, C>(d, stream, grid, g, M); break;
+    switch (conv_pro_mode(d)) {
+        GA_CONV3_MODES(GA_THIN)
         default: return GA_E_UNSUPPORTED;
     }
 #undef GA_THIN

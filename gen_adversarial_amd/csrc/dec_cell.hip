@@ -12,7 +12,7 @@
 // The weights of a chunk (32 rows of W1, 32 columns of W2: 16 / 32 KB as split bf16) go HBM / L2 -> registers a whole chunk
 // ahead and registers -> LDS at the top of their chunk: the B-fragments are then 16-B LDS reads (read straight from global
 // memory, one exposed L2 round trip per k step made the kernel 2-3x slower: one wave per SIMD hides nothing).
-// Contractions are the three-MFMA split-bf16 products of conv_bf3 (same operand split, same k order), the depthwise
+// Contractions are the three-MFMA split-bf16 products of conv_bf3 (split4 / mfma3 of conv_split.h, same k order), the depthwise
 // part is the fp32 loop of dwconv5 in the same order: the fused result is, bit for bit, that of the three launches it replaces
 // (tests/test_dec_cell_gpu.py, tests/test_fullsize_gpu.py).
 //
@@ -173,16 +173,12 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) dec_cell_fwd_kernel(const ga_
 #pragma unroll
                 for (int k = 0; k < KPJ; ++k)
 #pragma unroll
-                    for (int i = 0; i < TMW; ++i) {
-                        t1[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl[i][j * KPJ + k], bh[k], t1[i], 0, 0, 0);
-                        t1[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh[i][j * KPJ + k], bl[k], t1[i], 0, 0, 0);
-                        t1[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh[i][j * KPJ + k], bh[k], t1[i], 0, 0, 0);
-                    }
+                    for (int i = 0; i < TMW; ++i) mfma3(t1[i], xh[i][j * KPJ + k], xl[i][j * KPJ + k], bh[k], bl[k]);
                 floatx4 v = a[j] + bd4;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = silu_f(v[e]);
-                const bf16x4 hi = __builtin_convertvector(v, bf16x4);
-                const bf16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, floatx4), bf16x4);
+                bf16x4 hi, lo;
+                split4(v, hi, lo);
                 const int pj = p0 + (j / BW) * gm.W + (j % BW);                 // pixel of output j of the block
                 *reinterpret_cast<bf16x4*>(P2h + pj * DC_LDB + 4 * c4) = hi;
                 *reinterpret_cast<bf16x4*>(P2l + pj * DC_LDB + 4 * c4) = lo;
@@ -226,11 +222,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) dec_cell_fwd_kernel(const ga_
                     nl = *reinterpret_cast<const bf16x8*>(w2l + ((g + 1) >> 1) * 32 * WB::PITCH + ((g + 1) & 1) * 16);
                 }
 #pragma unroll
-                for (int i = 0; i < TMW; ++i) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i][ks], bh, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i][ks], bl, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i][ks], bh, acc[i][j], 0, 0, 0);
-                }
+                for (int i = 0; i < TMW; ++i) mfma3(acc[i][j], ah[i][ks], al[i][ks], bh, bl);
 #pragma unroll
                 for (int e = 0; e < EPG; ++e) {
                     const int idx = g * EPG + e, i = idx >> 4, r = idx & 15;
@@ -402,11 +394,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) dec_cell_bwd_kernel(const ga_
 #pragma unroll
                 for (int k = 0; k < KPJ; ++k)
 #pragma unroll
-                    for (int i = 0; i < TMW; ++i) {
-                        g[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gl[i][j * KPJ + k], bh[k], g[i], 0, 0, 0);
-                        g[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gh[i][j * KPJ + k], bl[k], g[i], 0, 0, 0);
-                        g[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gh[i][j * KPJ + k], bh[k], g[i], 0, 0, 0);
-                    }
+                    for (int i = 0; i < TMW; ++i) mfma3(g[i], gh[i][j * KPJ + k], gl[i][j * KPJ + k], bh[k], bl[k]);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) g2[j][e] = dsilu_f(g2[j][e] + bd4[e]);
                 interleave_mfma_valu<KPJ * TMW * 3, 44>();

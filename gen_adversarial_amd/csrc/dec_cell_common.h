@@ -1,12 +1,9 @@
 // Device helpers shared by the fused decoder-cell kernels (dec_cell.hip: whole-image workgroups; dec_cell_halo.hip: tiles with a
-// recomputed halo): split-bf16 fragments, the depthwise loops over an fp32 LDS plane, weight-chunk staging, SiLU.
+// recomputed halo): split-bf16 fragments (conv_split.h), the depthwise loops over an fp32 LDS plane, weight-chunk staging, SiLU.
 #pragma once
-#include "ga_common.h"
+#include "conv_split.h"
 
 namespace ga {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int DC_CH = 32;       // hidden channels per chunk
 constexpr int DC_PS = 40;       // floats per pixel of an fp32 LDS plane (32 + 8 pad)
@@ -26,14 +23,6 @@ __device__ unsigned long long ga_dc_trace_buf[8 * 16];
 #endif
 
 struct dc_geom { int lw, lhw, W, HW, PW, PH; };      // log2 W, log2 (H W); padded plane = (H + 4) x (W + 4)
-
-__device__ __forceinline__ void split8(const floatx4 a, const floatx4 b, bf16x8& hi, bf16x8& lo) {
-    const bf16x4 ha = __builtin_convertvector(a, bf16x4), hb = __builtin_convertvector(b, bf16x4);
-    const bf16x4 la = __builtin_convertvector(a - __builtin_convertvector(ha, floatx4), bf16x4);
-    const bf16x4 lb = __builtin_convertvector(b - __builtin_convertvector(hb, floatx4), bf16x4);
-    hi = __builtin_shufflevector(ha, hb, 0, 1, 2, 3, 4, 5, 6, 7);
-    lo = __builtin_shufflevector(la, lb, 0, 1, 2, 3, 4, 5, 6, 7);
-}
 
 // index of workgroup-local pixel p in the framed plane
 __device__ __forceinline__ int plane_idx(const int p, const dc_geom& g) {
@@ -63,11 +52,7 @@ __device__ __forceinline__ void gemm_resident(floatx16 (&acc)[TMW], const bf16x8
         const bf16x8 bh = *reinterpret_cast<const bf16x8*>(wh + ks * 16);
         const bf16x8 bl = *reinterpret_cast<const bf16x8*>(wl + ks * 16);
 #pragma unroll
-        for (int i = 0; i < TMW; ++i) {
-            acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i][ks], bh, acc[i], 0, 0, 0);
-            acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i][ks], bl, acc[i], 0, 0, 0);
-            acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i][ks], bh, acc[i], 0, 0, 0);
-        }
+        for (int i = 0; i < TMW; ++i) mfma3(acc[i], ah[i][ks], al[i][ks], bh, bl);
     }
 }
 
@@ -143,8 +128,6 @@ __device__ __forceinline__ int tile_pixel(const int s, const dc_geom& g) {
         return ni * g.HW + (rem / bpr) * BH * g.W + (rem % bpr) * BW;
     }
 }
-
-typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
 
 // One chunk of a [rows][K]-major split-bf16 weight matrix through LDS.  ROWMAJOR_K (the expand conv W1 and, backward, W2^T):
 // 32 rows (the chunk's hidden channels) x C columns, LDS pitch C + 8 elements.  Otherwise (the project conv W2, [C][Hd]):

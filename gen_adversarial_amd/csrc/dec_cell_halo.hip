@@ -12,7 +12,7 @@
 // Backward (d x from d t3 in ONE launch: with few channels the d x accumulator fits beside the operands): t1c is recomputed on the
 // 16 x 24 window (tile + 4), t2c and dt2c = (dt3 . W2c^T) * SiLU'(t2c) on the 12 x 20 window, dw5^T on the tile, * SiLU'(t1c),
 // and dx [128 x C] += dt1c [128 x 32] . W1c;  dx (+ addends) is written once.
-// Contractions are the three-MFMA split-bf16 products of conv_bf3 / ga_dec_cell (same operand split), the depthwise part the fp32
+// Contractions are the three-MFMA split-bf16 products of conv_bf3 / ga_dec_cell (split4 / mfma3 of conv_split.h), the depthwise part the fp32
 // loop of dwconv5 in the same tap order.
 #include "ga_common.h"
 #include "dec_cell_common.h"
@@ -188,8 +188,8 @@ __global__ void __launch_bounds__(256, 2) dec_cell_halo_fwd_kernel(const ga_dec_
                 floatx4 v = a[j] + bd4;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = silu_f(v[e]);
-                const bf16x4 hi = __builtin_convertvector(v, bf16x4);
-                const bf16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, floatx4), bf16x4);
+                bf16x4 hi, lo;
+                split4(v, hi, lo);
                 const int ip = oy * HT_W + ox + j;
                 *reinterpret_cast<bf16x4*>(P2h + ip * DC_LDB + 4 * c4) = hi;
                 *reinterpret_cast<bf16x4*>(P2l + ip * DC_LDB + 4 * c4) = lo;
@@ -206,9 +206,7 @@ __global__ void __launch_bounds__(256, 2) dec_cell_halo_fwd_kernel(const ga_dec_
             for (int j = 0; j < NT; ++j) {
                 const bf16x8 bh = *reinterpret_cast<const bf16x8*>(w2h + j * 32 * WB::PITCH + ks * 16);
                 const bf16x8 bl = *reinterpret_cast<const bf16x8*>(w2l + j * 32 * WB::PITCH + ks * 16);
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[j], 0, 0, 0);
+                mfma3(acc[j], ah, al, bh, bl);
             }
         }
         __syncthreads();                // the weight buffers, the taps and both planes are rewritten by the next chunk
@@ -478,8 +476,8 @@ __global__ void __launch_bounds__(256, 1) dec_cell_halo_bwd_kernel(const ga_dec_
             for (int j = 0; j < SW; ++j) {
                 const int ip = oy * HT_W + ox + j;
                 const floatx4 v = a[j] * *reinterpret_cast<const floatx4*>(P4 + ip * DC_PS + 4 * c4);
-                const bf16x4 hi = __builtin_convertvector(v, bf16x4);
-                const bf16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, floatx4), bf16x4);
+                bf16x4 hi, lo;
+                split4(v, hi, lo);
                 *reinterpret_cast<bf16x4*>(P2h + ip * DC_LDB + 4 * c4) = hi;
                 *reinterpret_cast<bf16x4*>(P2l + ip * DC_LDB + 4 * c4) = lo;
             }
@@ -497,9 +495,7 @@ __global__ void __launch_bounds__(256, 1) dec_cell_halo_bwd_kernel(const ga_dec_
             for (int j = 0; j < NT; ++j) {
                 const bf16x8 bh = *reinterpret_cast<const bf16x8*>(w3h + j * 32 * WB::PITCH + ks * 16);
                 const bf16x8 bl = *reinterpret_cast<const bf16x8*>(w3l + j * 32 * WB::PITCH + ks * 16);
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[j], 0, 0, 0);
+                mfma3(acc[j], ah, al, bh, bl);
             }
         }
         HC_T(13)
