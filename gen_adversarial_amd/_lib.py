@@ -200,7 +200,7 @@ class DecCellHaloDesc(C.Structure):
 class AvaeDesc(C.Structure):
     _fields_ = [('x', fp), ('a', fp), ('b', fp), ('c', fp), ('s', fp), ('dy', fp), ('y', fp), ('y2', fp),
                 ('mode', i32), ('backward', i32), ('N', i32), ('P', i32), ('C', i32), ('k', i32), ('H', i32), ('W', i32),
-                ('f0', f32), ('_reserved', i32)]
+                ('f0', f32), ('act_rep', i32)]
 
 
 class _OpUnion(C.Union):

@@ -7,6 +7,8 @@
 //   GA_AVAE_PIXELNORM  y = x * rsqrt(mean_c x^2 + 1e-8) with its backward (the style MLP's first layer sees the sampled latent,
 //                      which depends on the input image: unlike ga_pixelnorm it needs the adjoint)
 //   GA_AVAE_SAMPLE     m, v = halves of lrelu_0.2(t);  z = m + eps * exp(0.5 v) * temp   (Generator.forward, model.py:80-91)
+// Backward with K cotangents per forward row (act_rep = K, the K-cotangent backward plan): N counts cotangent rows and row n reads the
+// forward's tensors at row n / K; each cotangent row is the same work item, with the same summation order, as in a one-cotangent launch.
 // HBM-bound vector code; every reduction has a fixed order (bitwise reproducible).
 #include "ga_common.h"
 
@@ -23,8 +25,9 @@ __global__ void __launch_bounds__(256) avae_adain_kernel(const ga_avae_desc d, c
     const int c = chunk * 32 + 4 * c4;
     const bool cok = c < d.C;
     const floatx4 zero = {0.f, 0.f, 0.f, 0.f};
-    const float* t = d.x + (size_t)n * d.P * d.C;
-    const float* nz = d.a ? d.a + (size_t)n * d.P : nullptr;
+    const int nf = (d.backward && d.act_rep > 1) ? n / d.act_rep : n;      // row of the forward's tensors (t, noise, style, stats)
+    const float* t = d.x + (size_t)nf * d.P * d.C;
+    const float* nz = d.a ? d.a + (size_t)nf * d.P : nullptr;
     const floatx4 wn = (cok && d.b) ? *reinterpret_cast<const floatx4*>(d.b + c) : zero;
     if (!d.backward) {
         // InstanceNorm2d's variance is the mean of (u - mean)^2; E[u^2] - mean^2 in fp32 loses its digits when a channel's mean is
@@ -103,7 +106,7 @@ __global__ void __launch_bounds__(256) avae_adain_kernel(const ga_avae_desc d, c
         floatx4 mean = zero, rstd = zero;
         if (cok)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { mean[e] = d.s[((size_t)n * d.C + c + e) * 2]; rstd[e] = d.s[((size_t)n * d.C + c + e) * 2 + 1]; }
+            for (int e = 0; e < 4; ++e) { mean[e] = d.s[((size_t)nf * d.C + c + e) * 2]; rstd[e] = d.s[((size_t)nf * d.C + c + e) * 2 + 1]; }
         const float* dy = d.dy + (size_t)n * d.P * d.C;
         floatx4 s1 = zero, s2 = zero;
         if (cok)
@@ -131,7 +134,7 @@ __global__ void __launch_bounds__(256) avae_adain_kernel(const ga_avae_desc d, c
 #pragma unroll
         for (int e = 0; e < 4; ++e) { dbeta[e] = sm_a[4 * c4 + e]; dgamma[e] = sm_b[4 * c4 + e]; }
         const float invP = 1.0f / (float)d.P;
-        const floatx4 gr = *reinterpret_cast<const floatx4*>(d.c + (size_t)n * 2 * d.C + c) * rstd;
+        const floatx4 gr = *reinterpret_cast<const floatx4*>(d.c + (size_t)nf * 2 * d.C + c) * rstd;
         float* dt = d.y + (size_t)n * d.P * d.C;
         for (int p = pl; p < d.P; p += 32) {
             floatx4 pre = *reinterpret_cast<const floatx4*>(t + (size_t)p * d.C + c);
@@ -178,7 +181,7 @@ __global__ void __launch_bounds__(256) avae_pixelnorm_kernel(const ga_avae_desc 
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= d.N) return;
-    const float* x = d.x + row * d.C;
+    const float* x = d.x + ((d.backward && d.act_rep > 1) ? row / d.act_rep : row) * d.C;     // the forward's row
     float ss = 0.f, sd = 0.f;
     for (int c = lane; c < d.C; c += 64) {
         const float v = x[c];
@@ -201,8 +204,9 @@ __global__ void __launch_bounds__(256) avae_sample_kernel(const ga_avae_desc d, 
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const int c = (int)(i % d.C); long r = i / d.C;
         const int p = (int)(r % d.P); const long n = r / d.P;
-        const float tm = d.x[(n * d.P + p) * 2 * d.C + c], tv = d.x[(n * d.P + p) * 2 * d.C + d.C + c];
-        const float e = d.a[(n * d.C + c) * d.P + p];
+        const long nf = (d.backward && d.act_rep > 1) ? n / d.act_rep : n;      // row of the forward's t and eps
+        const float tm = d.x[(nf * d.P + p) * 2 * d.C + c], tv = d.x[(nf * d.P + p) * 2 * d.C + d.C + c];
+        const float e = d.a[(nf * d.C + c) * d.P + p];
         const float sg = expf(0.5f * lrelu02(tv)) * d.f0;
         if (!d.backward) {
             d.y[i] = lrelu02(tm) + e * sg;
@@ -229,6 +233,7 @@ extern "C" int ga_avae(const ga_avae_desc* d, void* s) {
     ga::clear_stale_error();
     if (!d || !d->x || !d->y || d->N <= 0 || d->C <= 0) return GA_E_BADARG;
     if (d->backward && !d->dy) return GA_E_BADARG;
+    if (d->act_rep > 1 && (!d->backward || d->N % d->act_rep)) return GA_E_BADARG;
     hipStream_t st = (hipStream_t)s;
     switch (d->mode) {
         case GA_AVAE_ADAIN: {

@@ -23,11 +23,20 @@ class _PreprocessDefense(torch.nn.Module, _EngineOwner):
         self._init_engines(base_classifier.device)
         self._store = base_classifier._store                      # share the folded classifier weights
 
-    def _make_engine(self, rows: int, rep: int, with_noise: bool = True) -> Engine:
+    @property
+    def supports_class_jacobian(self) -> bool:
+        from ...vgg_spec import VggSpec
+        return isinstance(self.base_classifier.classifier.spec, VggSpec)
+
+    def _make_engine(self, rows: int, rep: int, with_noise: bool = True, cot_rep: int = 1) -> Engine:
         w = self.base_classifier.classifier
         r = getattr(self, 'image_size', 64)
         return Engine(None, None, (3, r, r), w.state_dict, w.spec, rows=rows, rep=rep, alphas=[], device=self.device,
-                      store=self._store, noise_eps=self.noise_eps, blur=self.blur)
+                      store=self._store, noise_eps=self.noise_eps, blur=self.blur, cot_rep=cot_rep)
+
+    def class_jacobian_rows(self, batch: torch.Tensor, rep: int, classes=None):
+        self.image_size = batch.shape[-1]
+        return super().class_jacobian_rows(batch, rep, classes)
 
     def forward_rows(self, batch: torch.Tensor, rep: int = 1) -> torch.Tensor:
         self.image_size = batch.shape[-1]

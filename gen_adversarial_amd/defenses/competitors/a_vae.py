@@ -60,10 +60,15 @@ class AVaeDefenseModel(torch.nn.Module, _EngineOwner):
         self._init_engines(base_classifier.device)
         self.bpda = False
 
-    def _make_engine(self, rows: int, rep: int, with_noise: bool = True) -> Engine:
+    @property
+    def supports_class_jacobian(self) -> bool:
+        from ...vgg_spec import VggSpec
+        return isinstance(self.base_classifier.classifier.spec, VggSpec)
+
+    def _make_engine(self, rows: int, rep: int, with_noise: bool = True, cot_rep: int = 1) -> Engine:
         av, clf = self.purifier, self.base_classifier.classifier
         D = av.output_size
-        eng = Engine.bare(rows, device=self.device, store=self._store, rep=rep, resolution=(3, D, D), alphas=[])
+        eng = Engine.bare(rows, device=self.device, store=self._store, rep=rep, resolution=(3, D, D), alphas=[], cot_rep=cot_rep)
         return eng.build_avae_defense(av.state_dict, av.spec, self.kernel_size, clf.state_dict, clf.spec)
 
     def forward_rows(self, batch: torch.Tensor, rep: int = 1, preds_only: bool = True):

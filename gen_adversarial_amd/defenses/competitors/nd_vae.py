@@ -69,11 +69,16 @@ class NDVaeDefenseModel(torch.nn.Module, _EngineOwner):
         self._init_engines(base_classifier.device)
         self.bpda = False
 
-    def _make_engine(self, rows: int, rep: int, with_noise: bool = True) -> Engine:
+    @property
+    def supports_class_jacobian(self) -> bool:
+        from ...vgg_spec import VggSpec
+        return isinstance(self.base_classifier.classifier.spec, VggSpec)
+
+    def _make_engine(self, rows: int, rep: int, with_noise: bool = True, cot_rep: int = 1) -> Engine:
         nd, clf = self.purifier, self.base_classifier.classifier
         D = nd.cfg['input_dim']
         eng = Engine.bare(rows, device=self.device, store=self._store, rep=rep, resolution=(3, D, D), alphas=[],
-                          noise_eps=self.noise_std if with_noise else 0.0)
+                          noise_eps=self.noise_std if with_noise else 0.0, cot_rep=cot_rep)
         return eng.build_ndvae_defense(nd.state_dict, nd.spec, nd.h, clf.state_dict, clf.spec)
 
     def forward_rows(self, batch: torch.Tensor, rep: int = 1, preds_only: bool = True):

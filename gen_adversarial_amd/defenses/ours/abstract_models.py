@@ -195,7 +195,16 @@ class _EngineOwner:
             eng.noise.copy_(snap[1][0])
             eng.noise_coef.copy_(snap[1][1])
 
-    supports_class_jacobian = False          # owners whose _make_engine takes cot_rep (NVAE + VGG defender, VGG classifier)
+    # owners whose _make_engine takes cot_rep: the VGG classifier and, in front of it, the NVAE, ND-VAE, A-VAE and noise / blur defenders
+    supports_class_jacobian = False
+
+    def _n_classes(self):
+        """the classifier's class count (the columns of a whole class Jacobian), or None when this owner cannot tell"""
+        clf = getattr(self, 'base_classifier', None)
+        if clf is None:
+            clf = getattr(self, 'classifier', None)
+        weights = getattr(clf, 'classifier', clf)            # a classifier model holds its weights in `.classifier`
+        return getattr(weights, 'n_classes', None)
 
     def class_jacobian_rows(self, batch: torch.Tensor, rep: int, classes=None):
         """_EngineJacobian of (B,3,H,W) images under EoT `rep`, or None when this owner has no K-cotangent plan (callers then
@@ -204,10 +213,10 @@ class _EngineOwner:
             return None
         batch = batch.to(self.device, dtype=torch.float32).contiguous()
         rows = batch.shape[0] * rep
-        n_cols = classes.shape[1] if classes is not None else None
+        n_cols = classes.shape[1] if classes is not None else self._n_classes()
         K = max(1, self.jacobian_cot_rows // rows)
         if n_cols is not None:
-            K = min(K, n_cols)
+            K = min(K, n_cols)                               # no more cotangent rows than columns asked for
         if K < 2:
             return None
         eng = self._engine(rows, rep, True, cot_rep=K)

@@ -113,7 +113,8 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
         self.enc_rows = rows // rep if self.share_encoder else rows
         self.need_backward = need_backward
         if cot_rep < 1 or (cot_rep > 1 and not (self.has_nvae or isinstance(vgg_spec, VggSpec))):
-            raise ValueError('cot_rep > 1 (K-cotangent backward) is built for the NVAE + VGG defender and the VGG classifier')
+            raise ValueError('cot_rep > 1 (K-cotangent backward) is built for the defenders in front of a VGG classifier and for the '
+                             'VGG classifier itself')
         self.cot_rep = int(cot_rep)
         self.bytes = 0
         self.acts = {}                       # name -> Act (debugging / tests)
@@ -131,10 +132,15 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
     @classmethod
     def bare(cls, rows: int, device='cuda:0', precision: str = 'bf16x3', store: Optional[WeightStore] = None,
              dry_run: bool = False, rep: int = 1, resolution=None, alphas: Sequence[float] = (), noise_eps: float = 0.0,
-             need_backward: bool = True, blur: bool = False, share_encoder: bool = False, alpha_rows: bool = False) -> "Engine":
+             need_backward: bool = True, blur: bool = False, share_encoder: bool = False, alpha_rows: bool = False,
+             cot_rep: int = 1) -> "Engine":
         """An engine with empty plans: building blocks that are not yet part of a full defender (the StyleGAN2 layers of
         engine_stylegan.py) are emitted into it by their builders and closed with `finish()`; forward() / backward() then
-        replay the plans as for a full engine."""
+        replay the plans as for a full engine.
+        cot_rep = K > 1: K cotangents per forward row in the backward plan (see __init__), for the builders that thread it through
+        their own ops (build_ndvae_defense, build_avae_defense; each refuses a classifier without the plan)."""
+        if cot_rep < 1:
+            raise ValueError('cot_rep (cotangents per forward row of the backward plan) must be at least 1')
         self = cls.__new__(cls)
         self.device, self.dry_run, self.precision = torch.device(device), dry_run, precision
         if self.device.type != 'cuda' and not dry_run:
@@ -150,7 +156,7 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
         # draw runs once per image (see Engine.__init__); builders that support it read share_encoder / enc_rows
         self.share_encoder = bool(share_encoder) and rep > 1 and self.noise_eps == 0.0
         self.enc_rows = rows // rep if self.share_encoder else rows
-        self.need_backward, self.image_s2d, self.cot_rep = need_backward, False, 1
+        self.need_backward, self.image_s2d, self.cot_rep = need_backward, False, int(cot_rep)
         self.bytes, self.acts, self.version, self._sampler_descs, self._keep, self._frag_ok, self._thin_ok, self._pw_ok = 0, {}, 0, [], [], {}, {}, {}
         self.fwd, self.bwd, self._bwd_steps, self._scratch = L.Plan(), L.Plan(), [], {}
         self.eps, self.purified, self.dpurified, self._purified_grad_nhwc = [], None, None, None

@@ -6,6 +6,9 @@ the consumer, its derivative the PReLU epilogue of the backward GEMM, like the e
   image_io -> avg-pool k (ga_avae) -> [2x-1 as prologue] EncodeConvBlock x 3 -> sample (ga_avae) -> PixelNorm -> style MLP
   ConstantInput -> { [nearest x2 -> conv3x3 | transposed 4x4 / 2 conv] -> Blur } -> noise + LeakyReLU + AdaIN (ga_avae, one pass)
                -> conv3x3 -> noise + LeakyReLU + AdaIN -> ... -> to_rgb -> (x + 1) / 2 -> classifier
+
+With cot_rep = K > 1 (VGG classifier only) the backward plan carries K cotangents per forward row: every backward op counts R * K
+rows and reads the forward's tensors (activations, noise images, latent draw, AdaIN statistics: all R rows) at row n / K.
 """
 from __future__ import annotations
 
@@ -70,7 +73,7 @@ class AvaeBuilder:
 
         def backward():
             self._avae_op(self.bwd, name + '^T', L.GA_AVAE_ADAIN, x=t.t, a=noise, b=wn, c=gb.t, s=stats, dy=y.g, y=t.g, y2=gb.g,
-                          N=R, P=t.h * t.w, C=C, backward=1)
+                          N=R * self.cot_rep, P=t.h * t.w, C=C, backward=1, act_rep=self.cot_rep)
             t.g_written = gb.g_written = True
             self.grad_conv(name + '.style^T', gb.g, fc['w_bwd'], style_pre, K=1, dact_x=style_pre.t, dact_scale=sl, dact_shift=sl,
                            flags=L.GA_CONV_DACT_PRELU)
@@ -88,7 +91,9 @@ class AvaeBuilder:
         logits / dlogits, dx; the purified image is `purified_nhwc` (NHWC, pitch IMG_LD; not clamped, like the reference's)."""
         R, D = self.rows, aspec.output_size
         assert self.resolution[1] == D and D % kernel_size == 0 and D // kernel_size == aspec.enc_res, (self.resolution, D, kernel_size)
-        assert self.cot_rep == 1, 'K-cotangent plans are built for the NVAE + VGG defender'
+        if self.cot_rep != 1 and isinstance(cspec, ResNetSpec):
+            raise NotImplementedError('K-cotangent plans are built for the VGG classifier')
+        K = self.cot_rep            # cotangents per forward row: backward ops count R * K rows, forward tensors are read at row n / K
         self.nvae_sd = asd
         self.image_s2d = False
         self.share_encoder, self.enc_rows = False, R
@@ -103,7 +108,8 @@ class AvaeBuilder:
         self._avae_op(self.fwd, 'avae.avgpool', L.GA_AVAE_AVGPOOL, x=x0.t, y=xp.t, N=R, H=D, W=D, C=IMG_LD, k=kernel_size, backward=0)
 
         def bwd_pool():
-            self._avae_op(self.bwd, 'avae.avgpool^T', L.GA_AVAE_AVGPOOL, x=x0.t, dy=xp.g, y=x0.g, N=R, H=D, W=D, C=IMG_LD, k=kernel_size, backward=1)
+            self._avae_op(self.bwd, 'avae.avgpool^T', L.GA_AVAE_AVGPOOL, x=x0.t, dy=xp.g, y=x0.g, N=R * K, H=D, W=D, C=IMG_LD, k=kernel_size, backward=1,
+                          act_rep=K)
             x0.g_written = True
         self._bwd_steps.append(bwd_pool)
 
@@ -173,10 +179,10 @@ class AvaeBuilder:
                 self.grad_conv(f'avae.style.h{i}^T', hs[i].g, fcs[i]['w_bwd'], hs[i - 1], K=1, dact_x=hs[i - 1].t, dact_scale=sls,
                                dact_shift=sls, flags=L.GA_CONV_DACT_PRELU)
             self.grad_conv('avae.style.h0^T', hs[0].g, fcs[0]['w_bwd'], zn, K=1)
-            self._avae_op(self.bwd, 'avae.pixelnorm^T', L.GA_AVAE_PIXELNORM, x=z.t, dy=zn.g, y=z.g, N=R, C=16 * E, backward=1)
+            self._avae_op(self.bwd, 'avae.pixelnorm^T', L.GA_AVAE_PIXELNORM, x=z.t, dy=zn.g, y=z.g, N=R * K, C=16 * E, backward=1, act_rep=K)
             # d t4: the sample's adjoint WRITES the whole cotangent of the encoder's last conv output (its only consumer)
-            self._avae_op(self.bwd, 'avae.sample^T', L.GA_AVAE_SAMPLE, x=t4.t, a=self.eps[0], dy=z.g, y=t4.g, N=R, P=16, C=E,
-                          f0=TEMP_INFERENCE, backward=1)
+            self._avae_op(self.bwd, 'avae.sample^T', L.GA_AVAE_SAMPLE, x=t4.t, a=self.eps[0], dy=z.g, y=t4.g, N=R * K, P=16, C=E,
+                          f0=TEMP_INFERENCE, backward=1, act_rep=K)
             t4.g_written = True
         self._bwd_steps.append(bwd_mlp)
 

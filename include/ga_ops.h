@@ -456,6 +456,12 @@ int ga_dec_cell_halo_supported(int N, int H, int W, int C, int Hd);
  *   GA_AVAE_PIXELNORM x [N,C]: y = x * rsqrt(mean_c x^2 + 1e-8); backward (dy, x) -> y = dx
  *   GA_AVAE_SAMPLE    x = t [N,P,2C], a = eps [N,C,P] (NCHW): z[n,p,c] = lrelu(t[..c]) + eps * exp(0.5 lrelu(t[..C+c])) * f0;
  *                     backward dy = dz [N,P,C] -> y = dt [N,P,2C]
+ * act_rep = K > 1 (backward only; 0 and 1: one cotangent per forward row): K cotangents per forward row (the K-cotangent backward
+ *   plan).  N counts COTANGENT rows — dy, the written y and ADAIN's y2 = (d gamma | d beta) have N rows — and cotangent row n reads
+ *   the forward's tensors at row n / K: ADAIN x, a, c, s; PIXELNORM x; SAMPLE x, a.  AVGPOOL's adjoint reads no forward tensor
+ *   (act_rep accepted, no effect).  Every cotangent row keeps the summation order of a one-cotangent launch: a launch with
+ *   act_rep = K gives the bits of K launches with act_rep = 1 on the cotangent slices.  act_rep > 1 with backward == 0 or with
+ *   N % act_rep != 0: GA_E_BADARG.
  * ------------------------------------------------------------------------------------------------------------------ */
 enum { GA_AVAE_ADAIN = 0, GA_AVAE_AVGPOOL = 1, GA_AVAE_PIXELNORM = 2, GA_AVAE_SAMPLE = 3 };
 typedef struct ga_avae_desc {
@@ -463,7 +469,7 @@ typedef struct ga_avae_desc {
     float* y; float* y2;
     int mode, backward;
     int N, P, C, k, H, W;
-    float f0; int _reserved;
+    float f0; int act_rep;
 } ga_avae_desc;
 int ga_avae(const ga_avae_desc* d, void* stream);
 
@@ -621,6 +627,8 @@ long ga_debug_set_conv_row_limit(long bytes);
 const char* ga_last_hip_error(void);
 /* GA_ABI_VERSION is bumped with EVERY change of a descriptor's layout or meaning (a field added, a reserved field put to use) and
  * with every entry point added; the binding (gen_adversarial_amd/_lib.py: ABI_VERSION) refuses a library that reports another one. */
+/* (ga_avae_desc.act_rep took over a reserved int whose 0 keeps the former meaning: layout and every existing call unchanged, so
+ * the version stays.) */
 #define GA_ABI_VERSION 8
 int ga_abi_version(void);
 unsigned long ga_sizeof_op(void);
