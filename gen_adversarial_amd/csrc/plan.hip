@@ -4,39 +4,17 @@
 
 namespace ga { thread_local hipError_t g_last_err = hipSuccess; }
 
+// ga_axpby, ga_rep_sum and ga_pixelnorm take scalars: the adapters GA_OP_LIST names for them
+static int ga_run_axpby(const ga_axpby_desc* d, void* stream) { return ga_axpby(d->x, d->y, d->n, d->alpha, d->beta, stream); }
+static int ga_run_rep_sum(const ga_rep_sum_desc* d, void* stream) { return ga_rep_sum(d->x, d->y, d->rows, d->inner, d->rep, d->accumulate, stream); }
+static int ga_run_pixelnorm(const ga_pixelnorm_desc* d, void* stream) { return ga_pixelnorm(d->x, d->y, d->rows, d->C, stream); }
+
 static int run_one(const ga_op& op, void* stream) {
     switch (op.kind) {
-        case GA_OP_CONV:         return ga_conv2d(&op.u.conv, stream);
-        case GA_OP_DWCONV5:      return ga_dwconv5(&op.u.dw, stream);
-        case GA_OP_REDUCE:       return ga_rowchan_reduce(&op.u.red, stream);
-        case GA_OP_SE_EXCITE:    return ga_se_excite(&op.u.se, stream);
-        case GA_OP_SE_APPLY:     return ga_se_apply(&op.u.app, stream);
-        case GA_OP_BILINEAR_BWD: return ga_bilinear_up2_bwd(&op.u.bil, stream);
-        case GA_OP_SAMPLER:      return ga_sampler_mix(&op.u.smp, stream);
-        case GA_OP_DML:          return ga_dml_mean(&op.u.dml, stream);
-        case GA_OP_MAXPOOL:      return ga_maxpool2(&op.u.mp, stream);
-        case GA_OP_IMAGE_IO:     return ga_image_io(&op.u.io, stream);
-        case GA_OP_REP_SUM:      return ga_rep_sum(op.u.rs.x, op.u.rs.y, op.u.rs.rows, op.u.rs.inner, op.u.rs.rep, op.u.rs.accumulate, stream);
-        case GA_OP_BLUR:         return ga_gauss_blur(&op.u.blur, stream);
-        case GA_OP_INTERLEAVE2:  return ga_interleave2(&op.u.il, stream);
-        case GA_OP_MAXPOOL3S2:   return ga_maxpool3s2(&op.u.mp3, stream);
-        case GA_OP_AVGPOOL_ACT:  return ga_avgpool_act(&op.u.ap, stream);
-        case GA_OP_GCONV:        return ga_gconv(&op.u.gc, stream);
-        case GA_OP_PRELU:        return ga_prelu(&op.u.pr, stream);
-        case GA_OP_UNARY:        return ga_unary(&op.u.un, stream);
-        case GA_OP_MODOUT:       return ga_modout(&op.u.mo, stream);
-        case GA_OP_UP2_BLUR:     return ga_up2_blur(&op.u.ub, stream);
-        case GA_OP_PIXELNORM:    return ga_pixelnorm(op.u.pn.x, op.u.pn.y, op.u.pn.rows, op.u.pn.C, stream);
-        case GA_OP_LATENT_MIX:   return ga_latent_mix(&op.u.lm, stream);
-        case GA_OP_POOL_DENORM:  return ga_pool_denorm(&op.u.pd, stream);
-        case GA_OP_ATTN:         return ga_attn(&op.u.at, stream);
-        case GA_OP_LAYERNORM:    return ga_layernorm(&op.u.ln, stream);
-        case GA_OP_RESIZE2_CROP: return ga_resize2_crop(&op.u.rc, stream);
-        case GA_OP_DEC_CELL:     return ga_dec_cell(&op.u.dc, stream);
-        case GA_OP_AVAE:         return ga_avae(&op.u.av, stream);
-        case GA_OP_DEC_CELL_HALO: return ga_dec_cell_halo(&op.u.dh, stream);
-        case GA_OP_AXPBY:        return ga_axpby(op.u.ax.x, op.u.ax.y, op.u.ax.n, op.u.ax.alpha, op.u.ax.beta, stream);
-        default:                 return GA_E_UNSUPPORTED;
+#define GA_OP_CASE_(kind, value, member, desc, entry) case kind: return entry(&op.u.member, stream);
+        GA_OP_LIST(GA_OP_CASE_)
+#undef GA_OP_CASE_
+        default: return GA_E_UNSUPPORTED;
     }
 }
 

@@ -581,27 +581,51 @@ int ga_axpby(const float* x, float* y, long n, float alpha, float beta, void* st
 /* ------------------------------------------------------------------------------------------------------------------
  * Plans: a forward or backward pass is a flat list of the ops above, built once on the host and replayed by ONE call.
  * ------------------------------------------------------------------------------------------------------------------ */
-enum ga_op_kind { GA_OP_CONV = 1, GA_OP_DWCONV5 = 2, GA_OP_REDUCE = 3, GA_OP_SE_EXCITE = 4, GA_OP_SE_APPLY = 5,
-                  GA_OP_BILINEAR_BWD = 6, GA_OP_SAMPLER = 7, GA_OP_DML = 8, GA_OP_MAXPOOL = 9, GA_OP_IMAGE_IO = 10,
-                  GA_OP_AXPBY = 11, GA_OP_BLUR = 12, GA_OP_REP_SUM = 13, GA_OP_INTERLEAVE2 = 14, GA_OP_MAXPOOL3S2 = 15,
-                  GA_OP_AVGPOOL_ACT = 16, GA_OP_GCONV = 17, GA_OP_PRELU = 18, GA_OP_UNARY = 19,
-                  GA_OP_MODOUT = 20, GA_OP_UP2_BLUR = 21, GA_OP_PIXELNORM = 22, GA_OP_LATENT_MIX = 23,
-                  GA_OP_POOL_DENORM = 24, GA_OP_ATTN = 25, GA_OP_LAYERNORM = 26, GA_OP_RESIZE2_CROP = 27, GA_OP_DEC_CELL = 28,
-                  GA_OP_AVAE = 29, GA_OP_DEC_CELL_HALO = 30 };
 typedef struct ga_axpby_desc { const float* x; float* y; long n; float alpha, beta; } ga_axpby_desc;
 typedef struct ga_rep_sum_desc { const float* x; float* y; long rows, inner; int rep, accumulate; } ga_rep_sum_desc;
+typedef struct ga_pixelnorm_desc { const float* x; float* y; long rows; int C; } ga_pixelnorm_desc;
+/* The op list, one line per op: kind, its value (never reused), member of ga_op.u, descriptor type, and the function ga_plan_run
+ * calls with (&op.u.member, stream).  enum ga_op_kind and ga_op below, the dispatch in csrc/plan.hip and the whole Python binding
+ * (gen_adversarial_amd/_lib.py parses this header at import) are generated from it.  ga_axpby, ga_rep_sum and ga_pixelnorm take
+ * scalars, so their lines name adapters local to plan.hip. */
+#define GA_OP_LIST(X) \
+    X(GA_OP_CONV,          1, conv, ga_conv_desc,             ga_conv2d) \
+    X(GA_OP_DWCONV5,       2, dw,   ga_dwconv5_desc,          ga_dwconv5) \
+    X(GA_OP_REDUCE,        3, red,  ga_rowchan_reduce_desc,   ga_rowchan_reduce) \
+    X(GA_OP_SE_EXCITE,     4, se,   ga_se_excite_desc,        ga_se_excite) \
+    X(GA_OP_SE_APPLY,      5, app,  ga_se_apply_desc,         ga_se_apply) \
+    X(GA_OP_BILINEAR_BWD,  6, bil,  ga_bilinear_up2_bwd_desc, ga_bilinear_up2_bwd) \
+    X(GA_OP_SAMPLER,       7, smp,  ga_sampler_desc,          ga_sampler_mix) \
+    X(GA_OP_DML,           8, dml,  ga_dml_desc,              ga_dml_mean) \
+    X(GA_OP_MAXPOOL,       9, mp,   ga_maxpool2_desc,         ga_maxpool2) \
+    X(GA_OP_IMAGE_IO,     10, io,   ga_image_io_desc,         ga_image_io) \
+    X(GA_OP_AXPBY,        11, ax,   ga_axpby_desc,            ga_run_axpby) \
+    X(GA_OP_BLUR,         12, blur, ga_blur_desc,             ga_gauss_blur) \
+    X(GA_OP_REP_SUM,      13, rs,   ga_rep_sum_desc,          ga_run_rep_sum) \
+    X(GA_OP_INTERLEAVE2,  14, il,   ga_interleave2_desc,      ga_interleave2) \
+    X(GA_OP_MAXPOOL3S2,   15, mp3,  ga_maxpool3s2_desc,       ga_maxpool3s2) \
+    X(GA_OP_AVGPOOL_ACT,  16, ap,   ga_avgpool_act_desc,      ga_avgpool_act) \
+    X(GA_OP_GCONV,        17, gc,   ga_gconv_desc,            ga_gconv) \
+    X(GA_OP_PRELU,        18, pr,   ga_prelu_desc,            ga_prelu) \
+    X(GA_OP_UNARY,        19, un,   ga_unary_desc,            ga_unary) \
+    X(GA_OP_MODOUT,       20, mo,   ga_modout_desc,           ga_modout) \
+    X(GA_OP_UP2_BLUR,     21, ub,   ga_up2_blur_desc,         ga_up2_blur) \
+    X(GA_OP_PIXELNORM,    22, pn,   ga_pixelnorm_desc,        ga_run_pixelnorm) \
+    X(GA_OP_LATENT_MIX,   23, lm,   ga_latent_mix_desc,       ga_latent_mix) \
+    X(GA_OP_POOL_DENORM,  24, pd,   ga_pool_denorm_desc,      ga_pool_denorm) \
+    X(GA_OP_ATTN,         25, at,   ga_attn_desc,             ga_attn) \
+    X(GA_OP_LAYERNORM,    26, ln,   ga_layernorm_desc,        ga_layernorm) \
+    X(GA_OP_RESIZE2_CROP, 27, rc,   ga_resize2_crop_desc,     ga_resize2_crop) \
+    X(GA_OP_DEC_CELL,     28, dc,   ga_dec_cell_desc,         ga_dec_cell) \
+    X(GA_OP_AVAE,         29, av,   ga_avae_desc,             ga_avae) \
+    X(GA_OP_DEC_CELL_HALO, 30, dh,  ga_dec_cell_halo_desc,    ga_dec_cell_halo)
+#define GA_OP_ENUM_(kind, value, member, desc, entry) kind = value,
+#define GA_OP_MEMBER_(kind, value, member, desc, entry) desc member;
+enum ga_op_kind { GA_OP_LIST(GA_OP_ENUM_) };
 typedef struct ga_op {
     int kind;
     int _pad;
-    union {
-        ga_conv_desc conv; ga_dwconv5_desc dw; ga_rowchan_reduce_desc red; ga_se_excite_desc se; ga_se_apply_desc app;
-        ga_bilinear_up2_bwd_desc bil; ga_sampler_desc smp; ga_dml_desc dml; ga_maxpool2_desc mp; ga_image_io_desc io;
-        ga_axpby_desc ax; ga_blur_desc blur; ga_rep_sum_desc rs; ga_interleave2_desc il;
-        ga_maxpool3s2_desc mp3; ga_avgpool_act_desc ap; ga_gconv_desc gc; ga_prelu_desc pr;
-        ga_unary_desc un; ga_modout_desc mo; ga_up2_blur_desc ub; ga_latent_mix_desc lm; ga_pool_denorm_desc pd;
-        ga_attn_desc at; ga_layernorm_desc ln; ga_resize2_crop_desc rc; ga_dec_cell_desc dc; ga_avae_desc av; ga_dec_cell_halo_desc dh;
-        struct { const float* x; float* y; long rows; int C; } pn;
-    } u;
+    union { GA_OP_LIST(GA_OP_MEMBER_) } u;
 } ga_op;
 /* runs ops[0..n); returns 0 or the first failing op's error; *failed_index set when non-NULL */
 int ga_plan_run(const ga_op* ops, int n, void* stream, int* failed_index);
@@ -626,7 +650,8 @@ long ga_debug_set_conv_row_limit(long bytes);
 
 const char* ga_last_hip_error(void);
 /* GA_ABI_VERSION is bumped with EVERY change of a descriptor's layout or meaning (a field added, a reserved field put to use) and
- * with every entry point added; the binding (gen_adversarial_amd/_lib.py: ABI_VERSION) refuses a library that reports another one. */
+ * with every entry point added; the binding (gen_adversarial_amd/_lib.py reads it from this header) refuses a library that reports
+ * another one: a stale .so built from another header. */
 /* (ga_avae_desc.act_rep took over a reserved int whose 0 keeps the former meaning: layout and every existing call unchanged, so
  * the version stays.) */
 #define GA_ABI_VERSION 8

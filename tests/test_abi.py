@@ -3,10 +3,13 @@ arguments before touching the GPU (no compute calls here)."""
 import ctypes as C
 import os
 import re
+import subprocess
 
 from gen_adversarial_amd import _lib as L
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# the LLVM tools of the ROCm toolchain that builds the library (csrc/Makefile: HIPCC)
+LLVM = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')))), 'lib', 'llvm', 'bin')
 
 
 def _declared():
@@ -22,6 +25,14 @@ def test_every_declared_symbol_is_exported():
         assert getattr(L.lib, n) is not None
 
 
+def test_every_exported_symbol_is_declared():
+    """the other direction, from the built library: a ga_* function the header does not declare has no binding and no ABI count"""
+    out = subprocess.run([os.path.join(LLVM, 'llvm-readelf'), '--dyn-syms', '-W', L.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    rows = [line.split() for line in out.splitlines()]            # Num: Value Size Type Bind Vis Ndx Name
+    defined = {r[7] for r in rows if len(r) == 8 and r[6] != 'UND' and r[7].startswith('ga_')}
+    assert len(defined) >= 16 and defined <= set(_declared()), sorted(defined - set(_declared()))
+
+
 def test_every_direct_entry_point_takes_a_pointer_sized_stream():
     """L.run(desc, stream) passes the hipStream_t as the second argument: without argtypes ctypes would truncate it to a
     32-bit int (only the NULL stream would survive)"""
@@ -30,6 +41,16 @@ def test_every_direct_entry_point_takes_a_pointer_sized_stream():
         assert fn.argtypes is not None and len(fn.argtypes) == 2, name
         assert fn.argtypes[0] is C.POINTER(desc_type) and fn.argtypes[1] is C.c_void_p, name
         assert fn.restype is C.c_int, name
+    src = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'ga_ops.h')).read(), flags=re.S)
+    protos = re.findall(r'^\s*([\w ]+?[\w*])\s*\b(ga_\w+)\s*\(([^()]*)\)\s*;', src, flags=re.M)
+    assert sorted(p[1] for p in protos) == _declared()
+    for result, name, params in protos:
+        fn = getattr(L.lib, name)
+        nargs = 0 if params.strip() == 'void' else params.count(',') + 1
+        assert fn.argtypes is not None and len(fn.argtypes) == nargs, name
+        assert fn.restype is {'int': C.c_int, 'long': C.c_long, 'unsigned long': C.c_ulong, 'const char*': C.c_char_p}[result], name
+        for typ, param in zip(fn.argtypes, params.split(',')):          # a pointer stays pointer-sized, a scalar keeps its C type
+            assert ('*' in param) == (typ is C.c_void_p or hasattr(typ, 'contents')), (name, param)
 
 
 def test_struct_sizes_and_version():
