@@ -794,6 +794,67 @@ __global__ void __launch_bounds__(256) latent_mix_kernel(const ga_latent_mix_des
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// alpha cotangents: d loss / d alpha of the two interpolations above, one float per row (ga_sampler_desc.mode == 2,
+// ga_latent_mix_desc.backward == 2).  Neither reads alpha.  Fixed summation order, no atomics: a row's bits depend on its own
+// data alone (not on N, the grid or the workgroup that ran it).
+// ---------------------------------------------------------------------------------------------------------------
+// z = (1 - a) enc_mu + a (eps sigma + dec_mu)  =>  dL/da[n] = sum_{p, c < NL} dz * (eps sigma + dec_mu - enc_mu).
+// One workgroup per cotangent row.  Summation tree: thread t adds the terms t, t + 256, ... in that order (ceil(T / 256) additions,
+// T = h w NL), six __shfl_xor steps per wave, then thread 0 adds the four waves' partials in wave order (3 additions).
+__global__ void __launch_bounds__(256) sampler_alpha_grad_kernel(const ga_sampler_desc d) {
+    __shared__ float wave_sum[4];
+    const int hw = d.h * d.w, T = hw * d.NL;
+    const int ldz = d.ldz > 0 ? d.ldz : d.NL;
+    for (long n = blockIdx.x; n < d.N; n += gridDim.x) {
+        const long nq = d.q_rep > 1 ? n / d.q_rep : n;
+        float acc = 0.f;
+        for (int i = threadIdx.x; i < T; i += 256) {
+            const int c = i % d.NL, p = i / d.NL;
+            const long pix = n * hw + p;
+            const float mq = d.mu_q[(nq * hw + p) * d.ldq + c];
+            const float mp = d.p ? d.p[pix * d.ldp + c] : 0.f;
+            const float ls = d.p ? d.p[pix * d.ldp + d.NL + c] : 0.f;
+            const float e = d.eps_nchw ? d.eps[((size_t)n * d.NL + c) * hw + p] : d.eps[pix * d.NL + c];
+            const float sig = d.temp * expf(softclamp5(ls));
+            const float smp = e * sig + softclamp5(mp);
+            acc += d.dz[pix * ldz + c] * (smp - softclamp5(mp + mq));
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        __syncthreads();                                        // the previous row's partials have been read
+        if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0)
+            d.z[(size_t)n * d.alpha_ld + d.alpha_col] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+    }
+}
+
+// out = (1 - a) (codes + avg) + a styles  =>  dL/da[r, j] = sum_D dout * (styles - (codes + avg)).  One wavefront per (r, j), as
+// pixelnorm_kernel per row.  Summation tree: lane l adds its quads l, l + 64, ... (4 additions per quad: three inside it, one into
+// the lane's sum), then six __shfl_xor steps.
+__global__ void __launch_bounds__(256) latent_alpha_grad_kernel(const ga_latent_mix_desc d, const long items) {
+    const int lane = threadIdx.x & 63;
+    const int D4 = d.D / 4;
+    const int rep = d.rep > 1 ? d.rep : 1;
+    for (long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6); i < items; i += (long)gridDim.x * 4) {     // i = r * J + j
+        const long r = i / d.J; const int j = (int)(i - r * d.J);
+        const float* so = d.styles + i * d.D;
+        const float* go = d.dout + i * d.D;
+        const float* co = d.codes + ((r / rep) * d.J + j) * d.D;
+        float acc = 0.f;
+        for (int q = lane; q < D4; q += 64) {
+            floatx4 c = ld4(co + 4 * q);
+            if (d.avg) c += ld4(d.avg + (size_t)j * d.D + 4 * q);
+            const floatx4 t = ld4(go + 4 * q) * (ld4(so + 4 * q) - c);
+            acc += ((t[0] + t[1]) + t[2]) + t[3];
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        if (lane == 0) d.out[i] = acc;
+    }
+}
+
 __global__ void __launch_bounds__(256) pool_denorm_kernel(const ga_pool_denorm_desc d, const long total) {
     const int k = d.k, Wi = d.W * k;
     if (!d.backward) {
@@ -1312,8 +1373,21 @@ extern "C" int ga_bilinear_up2_bwd(const ga_bilinear_up2_bwd_desc* d, void* s) {
     return check_launch();
 }
 
+// mode 2: the alpha cotangent of the mode-0 interpolation, one float per cotangent row at z[n * alpha_ld + alpha_col]
+static int sampler_alpha_grad(const ga_sampler_desc* d, void* s) {
+    if (!d->mu_q || !d->eps || !d->dz || !d->z || d->N <= 0 || d->h <= 0 || d->w <= 0 || d->NL <= 0) return GA_E_BADARG;
+    if (d->backward != 1 || d->act_rep > 1) return GA_E_BADARG;
+    if (d->ldq < d->NL || (d->p && d->ldp < 2 * d->NL) || (d->ldz != 0 && d->ldz < d->NL)) return GA_E_BADARG;
+    if (d->alpha_col < 0 || d->alpha_ld <= d->alpha_col) return GA_E_BADARG;
+    if (d->q_rep > 1 && d->N % d->q_rep) return GA_E_BADARG;
+    if ((long)d->h * d->w * d->NL > 0x7fffffffL) return GA_E_UNSUPPORTED;
+    hipLaunchKernelGGL(sampler_alpha_grad_kernel, dim3((unsigned)d->N), dim3(256), 0, (hipStream_t)s, *d);
+    return check_launch();
+}
+
 extern "C" int ga_sampler_mix(const ga_sampler_desc* d, void* s) {
     ga::clear_stale_error();
+    if (d && d->mode == 2) return sampler_alpha_grad(d, s);
     if (!d || !d->mu_q || !d->eps || d->N <= 0 || d->h <= 0 || d->w <= 0 || d->NL <= 0) return GA_E_BADARG;
     if (d->ldq < d->NL || (d->p && d->ldp < 2 * d->NL)) return GA_E_BADARG;
     if (!d->backward && !d->z) return GA_E_BADARG;
@@ -1436,8 +1510,20 @@ extern "C" int ga_pixelnorm(const float* x, float* y, long rows, int C, void* s)
     return check_launch();
 }
 
+// backward == 2: the alpha cotangent of the mix, a dense [R, J] table through `out`
+static int latent_alpha_grad(const ga_latent_mix_desc* d, void* s) {
+    if (!d->dout || !d->styles || !d->codes || !d->out || d->R <= 0 || d->J <= 0 || d->D <= 0) return GA_E_BADARG;
+    if (d->D % 4) return GA_E_UNSUPPORTED;
+    if (d->rep > 1 && d->R % d->rep) return GA_E_BADARG;
+    if (!aligned16(d->dout) || !aligned16(d->styles) || !aligned16(d->codes) || (d->avg && !aligned16(d->avg))) return GA_E_ALIGN;
+    const long items = (long)d->R * d->J, blocks = (items + 3) / 4;
+    hipLaunchKernelGGL(latent_alpha_grad_kernel, dim3((unsigned)(blocks > 65535 ? 65535 : blocks)), dim3(256), 0, (hipStream_t)s, *d, items);
+    return check_launch();
+}
+
 extern "C" int ga_latent_mix(const ga_latent_mix_desc* d, void* s) {
     ga::clear_stale_error();
+    if (d && d->backward == 2) return latent_alpha_grad(d, s);
     if (!d || !d->alpha || d->R <= 0 || d->J <= 0 || d->D <= 0) return GA_E_BADARG;
     if (d->D % 4) return GA_E_UNSUPPORTED;
     if (!d->backward && (!d->codes || !d->styles || !d->out)) return GA_E_BADARG;

@@ -135,7 +135,14 @@ class _EngineOwner:
     supports_forward_only = False
 
     def _engine(self, rows: int, rep: int, with_noise: bool = True, cot_rep: int = 1, forward_only: bool = False,
-                alpha_rows: bool = False) -> Engine:
+                alpha_rows: bool = False, alpha_grad: bool = False) -> Engine:
+        if alpha_grad:          # differentiable engine whose backward plan also reduces d loss / d alpha (loss_and_alpha_grad)
+            key = (rows, rep, with_noise, 'alpha_grad')
+            if key not in self._engines:
+                self._engines[key] = self._make_engine(rows, rep, with_noise, alpha_grad=True)
+            eng = self._engines[key]
+            eng.set_alphas(self._current_alphas())
+            return eng
         if alpha_rows:          # candidate-batched forward-only engine: its alphas are a per-row table the caller fills
             key = (rows, rep, with_noise, 'alpha_rows')
             if key not in self._engines:
@@ -352,6 +359,34 @@ class MLVGMDefenseModel(ABC, _EngineOwner):
             return logits
         purified = eng.purified.clone() if eng.purified is not None else eng.purified_nchw()
         return logits, purified.view(B, K, rep, *purified.shape[1:])
+
+    @torch.no_grad()
+    def loss_and_alpha_grad(self, batch: torch.Tensor, labels: torch.Tensor, rep: int = 1):
+        """(loss [B], dalpha [B, n]) from ONE forward and ONE backward replay of an `alpha_grad` engine: the cross-entropy of the
+        EoT-mean logits of every image (the quantity the attacks differentiate) and its exact gradient in the interpolation alphas
+        AS STORED in `interpolation_alphas` (attenuation already applied).  Logit cotangent of replica row (b, e):
+        (softmax(mean_b) - onehot(label_b)) / rep; dalpha[b] is the sum of the engine's per-row table over the image's rep rows.
+        Fresh latent (and input-noise) draws per call, as for every other call; fixed_noise(...) is honoured."""
+        if batch.dim() != 4 or batch.shape[1] != 3:
+            raise ValueError('expected a (B, 3, H, W) image batch')
+        batch = batch.to(self.device, dtype=torch.float32).contiguous()
+        B = batch.shape[0]
+        labels = torch.as_tensor(labels).to(self.device, dtype=torch.long).view(B)
+        eng = self._engine(B * rep, rep, True, alpha_grad=True)
+        if tuple(batch.shape[2:]) != tuple(eng.resolution[1:]):
+            raise ValueError(f'expected {eng.resolution[1]}x{eng.resolution[2]} images, got {tuple(batch.shape[2:])}')
+        eng.x_in.copy_(batch)
+        self._fill_noise(eng)
+        eng.forward()
+        eng.version += 1
+        mean = eng.logits.view(B, rep, -1).mean(dim=1)
+        logp = torch.log_softmax(mean, dim=1)
+        loss = -logp.gather(1, labels.view(B, 1)).view(B)
+        cot = logp.exp()
+        cot.scatter_add_(1, labels.view(B, 1), cot.new_full((B, 1), -1.0))
+        eng.dlogits.view(B, rep, -1).copy_((cot / rep).view(B, 1, -1).expand(B, rep, cot.shape[1]))
+        eng.backward()
+        return loss, eng.alpha_grads().view(B, rep, -1).sum(dim=1)
 
     def purify(self, batch: torch.Tensor) -> torch.Tensor:
         """(B,3,H,W) pre-processed images -> purified reconstructions (no input noise / blur: those belong to

@@ -70,13 +70,14 @@ class NVAEDefenseModel(MLVGMDefenseModel, torch.nn.Module):
     supports_forward_only = True
 
     def _make_engine(self, rows: int, rep: int, with_noise: bool = True, cot_rep: int = 1, need_backward: bool = True,
-                     alpha_rows: bool = False) -> Engine:
+                     alpha_rows: bool = False, alpha_grad: bool = False) -> Engine:
         ae, clf = self.autoencoder, self.classifier.classifier
         return Engine(ae.state_dict, ae.config, ae.resolution, clf.state_dict, clf.spec, rows=rows, rep=rep,
                       alphas=self.interpolation_alphas, temperature=self.temperature,
                       noise_eps=self.eps if with_noise else 0.0, blur=self.blur_input and with_noise,
                       share_encoder=True,      # EoT replicas share the encoder pass whenever no input noise is drawn
-                      device=self.device, store=self._store, cot_rep=cot_rep, need_backward=need_backward, alpha_rows=alpha_rows)
+                      device=self.device, store=self._store, cot_rep=cot_rep, need_backward=need_backward, alpha_rows=alpha_rows,
+                      alpha_grad=alpha_grad)
 
 
 class E4EStyleGanDefenseModel(MLVGMDefenseModel, torch.nn.Module):
@@ -99,13 +100,14 @@ class E4EStyleGanDefenseModel(MLVGMDefenseModel, torch.nn.Module):
     def load_autoencoder(self, model_path: str, device: str) -> E4EWeights:
         return load_E4EStyleGan(model_path, device)
 
-    def _make_engine(self, rows: int, rep: int, with_noise: bool = True, need_backward: bool = True, alpha_rows: bool = False) -> Engine:
+    def _make_engine(self, rows: int, rep: int, with_noise: bool = True, need_backward: bool = True, alpha_rows: bool = False,
+                     alpha_grad: bool = False) -> Engine:
         ae, clf = self.autoencoder, self.classifier.classifier
         res = getattr(self, 'image_size', 256)
         eng = Engine.bare(rows, device=self.device, store=self._store, rep=rep, resolution=(3, res, res),
                           alphas=self.interpolation_alphas, noise_eps=self.eps if with_noise else 0.0,
                           blur=self.blur_input and with_noise, need_backward=need_backward, alpha_rows=alpha_rows,
-                          share_encoder=True)      # EoT replicas share the encoder pass whenever no input noise is drawn
+                          alpha_grad=alpha_grad, share_encoder=True)      # EoT replicas share the encoder pass whenever no input noise is drawn
         size = ae.decoder_spec.size
         return eng.build_e4e_defense(ae.encoder_sd, ae.encoder_spec, ae.decoder_sd, ae.decoder_spec, ae.latent_avg,
                                      clf.state_dict, clf.spec, pool_to=min(256, size))
@@ -117,6 +119,10 @@ class E4EStyleGanDefenseModel(MLVGMDefenseModel, torch.nn.Module):
     def forward_candidates(self, batch: torch.Tensor, alphas, rep: int = 1, preds_only: bool = True):
         self.image_size = batch.shape[-1]
         return super().forward_candidates(batch, alphas, rep, preds_only)
+
+    def loss_and_alpha_grad(self, batch: torch.Tensor, labels: torch.Tensor, rep: int = 1):
+        self.image_size = batch.shape[-1]
+        return super().loss_and_alpha_grad(batch, labels, rep)
 
     def purify(self, batch: torch.Tensor) -> torch.Tensor:
         """normalised images (B,3,H,W) in [-1, 1] -> normalised reconstructions, as the reference's purify (models.py:105-132);
@@ -146,12 +152,14 @@ class TransStyleGanDefenseModel(MLVGMDefenseModel, torch.nn.Module):
     def load_autoencoder(self, model_path: str, device: str) -> TransWeights:
         return load_TranStyleGan(model_path, device)
 
-    def _make_engine(self, rows: int, rep: int, with_noise: bool = True, need_backward: bool = True, alpha_rows: bool = False) -> Engine:
+    def _make_engine(self, rows: int, rep: int, with_noise: bool = True, need_backward: bool = True, alpha_rows: bool = False,
+                     alpha_grad: bool = False) -> Engine:
         ae, clf = self.autoencoder, self.classifier.classifier
         res = getattr(self, 'image_size', 128)
         eng = Engine.bare(rows, device=self.device, store=self._store, rep=rep, resolution=(3, res, res),
                           alphas=self.interpolation_alphas, noise_eps=self.eps if with_noise else 0.0,
-                          blur=self.blur_input and with_noise, share_encoder=True, need_backward=need_backward, alpha_rows=alpha_rows)
+                          blur=self.blur_input and with_noise, share_encoder=True, need_backward=need_backward, alpha_rows=alpha_rows,
+                          alpha_grad=alpha_grad)
         # reference sizes: resize to 256 (2 x the 128-px cars images), crop 32 rows top and bottom; scaled with the image for
         # reduced test inputs
         return eng.build_trans_defense(ae.encoder_sd, ae.encoder_spec, ae.decoder_sd, ae.decoder_spec, ae.latent_avg,
@@ -164,6 +172,10 @@ class TransStyleGanDefenseModel(MLVGMDefenseModel, torch.nn.Module):
     def forward_candidates(self, batch: torch.Tensor, alphas, rep: int = 1, preds_only: bool = True):
         self.image_size = batch.shape[-1]
         return super().forward_candidates(batch, alphas, rep, preds_only)
+
+    def loss_and_alpha_grad(self, batch: torch.Tensor, labels: torch.Tensor, rep: int = 1):
+        self.image_size = batch.shape[-1]
+        return super().loss_and_alpha_grad(batch, labels, rep)
 
     def purify(self, batch: torch.Tensor) -> torch.Tensor:
         """normalised images (B,3,H,W) in [-1, 1] -> normalised reconstructions, as the reference's purify (models.py:299-353)"""

@@ -34,3 +34,8 @@ class EoTWrapper(torch.nn.Module):
         autograd backward per class, like the reference (src/attacks/untargeted.py:526-560, :605-635)."""
         fast = getattr(self.model, 'class_jacobian_rows', None)
         return fast(x, self.eot_steps, classes) if fast is not None else None
+
+    def loss_and_alpha_grad(self, x: torch.Tensor, labels: torch.Tensor):
+        """(loss [B], dalpha [B, n]): cross-entropy of the EoT-mean logits and its gradient in the wrapped defender's interpolation
+        alphas, from one forward and one backward pass over B * eot_steps rows (MLVGMDefenseModel.loss_and_alpha_grad)"""
+        return self.model.loss_and_alpha_grad(x, labels, rep=self.eot_steps)

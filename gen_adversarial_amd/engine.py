@@ -74,14 +74,17 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
                  alphas: Sequence[float], temperature: float = 0.6, noise_eps: float = 0.0,
                  device: str = 'cuda:0', need_backward: bool = True, dry_run: bool = False,
                  store: Optional[WeightStore] = None, precision: str = 'bf16x3', blur: bool = False,
-                 share_encoder: bool = False, cot_rep: int = 1, alpha_rows: bool = False):
+                 share_encoder: bool = False, cot_rep: int = 1, alpha_rows: bool = False, alpha_grad: bool = False):
         """alpha_rows: the interpolation alphas are a per-row device table (`alpha_table`, filled by set_alpha_rows / set_alphas) read
         by every sampler: rows of one image may carry different alpha vectors — K candidates x E EoT replicas with rep = K * E share
         that image's encoder pass (alpha learning, src/experiments/alpha_learning/common_utils.py:81-103).
         cot_rep = K > 1: the backward plan takes K cotangents per forward row in ONE replay (the per-class
         backward loops of DeepFool / FAB, src/attacks/untargeted.py:526-560, :605-635).  `dlogits` is then [rows * K, classes]
         (cotangent k of defender row r at row r * K + k) and `dx` [images * K, 3, H, W] (gradient k of image b at row b * K + k);
-        every saved activation is read by its K cotangent rows, nothing is recomputed or copied."""
+        every saved activation is read by its K cotangent rows, nothing is recomputed or copied.
+        alpha_grad: the backward plan also reduces d loss / d alpha of every latent group, per row, beside that group's sampler
+        backward (ga_sampler_desc.mode == 2) into `alpha_grad_rows` [rows, groups]; read it with alpha_grads() after backward().
+        One cotangent per row only (cot_rep == 1), and it needs the backward plan."""
         if rows % rep:
             raise ValueError('rows must be a multiple of the EoT repeat')
         self.device = torch.device(device)
@@ -116,6 +119,7 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
             raise ValueError('cot_rep > 1 (K-cotangent backward) is built for the defenders in front of a VGG classifier and for the '
                              'VGG classifier itself')
         self.cot_rep = int(cot_rep)
+        self._init_alpha_grad(alpha_grad)
         self.bytes = 0
         self.acts = {}                       # name -> Act (debugging / tests)
         self.version = 0                     # bumped by callers after each forward (stale-backward detection)
@@ -133,12 +137,14 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
     def bare(cls, rows: int, device='cuda:0', precision: str = 'bf16x3', store: Optional[WeightStore] = None,
              dry_run: bool = False, rep: int = 1, resolution=None, alphas: Sequence[float] = (), noise_eps: float = 0.0,
              need_backward: bool = True, blur: bool = False, share_encoder: bool = False, alpha_rows: bool = False,
-             cot_rep: int = 1) -> "Engine":
+             cot_rep: int = 1, alpha_grad: bool = False) -> "Engine":
         """An engine with empty plans: building blocks that are not yet part of a full defender (the StyleGAN2 layers of
         engine_stylegan.py) are emitted into it by their builders and closed with `finish()`; forward() / backward() then
         replay the plans as for a full engine.
         cot_rep = K > 1: K cotangents per forward row in the backward plan (see __init__), for the builders that thread it through
-        their own ops (build_ndvae_defense, build_avae_defense; each refuses a classifier without the plan)."""
+        their own ops (build_ndvae_defense, build_avae_defense; each refuses a classifier without the plan).
+        alpha_grad: as for __init__, for the builders with interpolation alphas (build_e4e_defense, build_trans_defense: one
+        ga_latent_mix_desc.backward == 2 op beside latent_mix^T)."""
         if cot_rep < 1:
             raise ValueError('cot_rep (cotangents per forward row of the backward plan) must be at least 1')
         self = cls.__new__(cls)
@@ -157,6 +163,7 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
         self.share_encoder = bool(share_encoder) and rep > 1 and self.noise_eps == 0.0
         self.enc_rows = rows // rep if self.share_encoder else rows
         self.need_backward, self.image_s2d, self.cot_rep = need_backward, False, int(cot_rep)
+        self._init_alpha_grad(alpha_grad)
         self.bytes, self.acts, self.version, self._sampler_descs, self._keep, self._frag_ok, self._thin_ok, self._pw_ok = 0, {}, 0, [], [], {}, {}, {}
         self.fwd, self.bwd, self._bwd_steps, self._scratch = L.Plan(), L.Plan(), [], {}
         self.eps, self.purified, self.dpurified, self._purified_grad_nhwc = [], None, None, None
@@ -172,6 +179,20 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
             # candidates x replicas of an image share its encoder pass; input noise makes every row its own encoder input
             raise ValueError('a per-row alpha engine with rep > 1 shares the encoder pass of an image between its rows: '
                              'not available with input noise (initial_noise_eps > 0)')
+
+    def _init_alpha_grad(self, alpha_grad: bool):
+        self.alpha_grad, self.alpha_grad_rows = bool(alpha_grad), None
+        if self.alpha_grad and self.cot_rep > 1:
+            raise ValueError('alpha_grad reduces one cotangent per row: not available together with cot_rep > 1')
+        if self.alpha_grad and not self.need_backward:
+            raise ValueError('alpha_grad lives in the backward plan: not available with need_backward=False')
+
+    def alpha_grads(self) -> torch.Tensor:
+        """[rows, n]: d loss / d alpha per row and latent group (latent index) for the cotangent of the last backward(), with respect
+        to the alphas as the engine holds them; the gradient of an image is the sum over its `rep` rows"""
+        if self.alpha_grad_rows is None:
+            raise RuntimeError('engine was built without the alpha-gradient ops (alpha_grad=True)')
+        return self.alpha_grad_rows
 
     def _alloc_alpha_table(self, n: int, pairs: bool) -> torch.Tensor:
         """the per-row table [rows, 2 n] of (alpha, 1 - alpha) pairs (NVAE samplers) or [rows, n] (latent mixing), every row = self.alphas"""

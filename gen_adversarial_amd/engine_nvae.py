@@ -201,6 +201,8 @@ class NvaeBuilder:
         self.purified = self.alloc((R, 3, H, H))                            # NCHW
         if self.alpha_rows:                       # per-row (alpha, 1 - alpha) pairs, one column pair per latent group
             self._alloc_alpha_table(len(spec.groups), pairs=True)
+        if self.alpha_grad:                       # d loss / d alpha per row, one column per latent group (Engine.alpha_grads)
+            self.alpha_grad_rows = self.alloc((R, len(spec.groups)))
 
         # ---- stem: normalisation (x-0.5)/0.5 as prologue affine, then weight-normed 3x3 (model.py:106-107)
         stem = self.devd('stem', lambda: F.pad_image_conv(F.fold_wn_conv(nvae_sd, 'preprocessing_block.init_conv'), 3, IMG_LD))
@@ -343,6 +345,15 @@ class NvaeBuilder:
         self._sampler_alpha_rows(d, eps)
         self._sampler_descs.append((d, [i for i, e in enumerate(self.eps) if e is eps][0]))
         self.bwd.add(d, name)
+        if self.alpha_grad:
+            # the alpha cotangent reads z.g as the op above just did: z.g is written once, by the combiner's transposed conv(s) in
+            # front of it, and the sampler's backward writes dmu_q / dmu_q_rows / dp only.  No alpha in it: not in _sampler_descs
+            g = L.SamplerDesc()
+            g.mu_q, g.ldq, g.p, g.ldp, g.eps, g.eps_nchw, g.dz = d.mu_q, d.ldq, d.p, d.ldp, d.eps, 1, d.dz
+            g.N, g.h, g.w, g.NL, g.ldz, g.temp, g.q_rep = nc, z.h, z.w, self.spec.num_latent, z.c, self.temperature, q_rep
+            g.backward, g.mode, g.z = 1, 2, _ptr(self.alpha_grad_rows)
+            g.alpha_ld, g.alpha_col = self.alpha_grad_rows.shape[1], [i for i, e in enumerate(self.eps) if e is eps][0]
+            self.bwd.add(g, name + '.dalpha')
         if q_rep > 1:
             self.rep_sum(name + '.rep_sum', rows_grad, muq, q_rep)
         muq.g_written = True

@@ -243,6 +243,8 @@ class StyleGanBuilder:
             self.alpha_dev = alpha_src = self.alloc((J,))
             self.alpha_dev.copy_(torch.tensor(self.alphas, dtype=torch.float32))
             alpha_ld = 0
+        if self.alpha_grad:                                      # d loss / d alpha per row and latent index (Engine.alpha_grads)
+            self.alpha_grad_rows = self.alloc((R, J))
         latent = Act(self, R, 1, 1, J * D, 'sg.latent')
         mx = L.LatentMixDesc()
         mx.codes, mx.avg, mx.styles, mx.alpha, mx.out = _ptr(codes), _ptr(avg), _ptr(styles), _ptr(alpha_src), _ptr(latent.t)
@@ -254,6 +256,11 @@ class StyleGanBuilder:
             b.alpha, b.dout, b.dcodes, b.R, b.J, b.D, b.backward = _ptr(alpha_src), _ptr(latent.g), _ptr(dcodes), R, J, D, 1
             b.rep, b.alpha_ld = R // self.enc_rows, alpha_ld
             self.bwd.add(b, 'latent_mix^T')
+            if self.alpha_grad:                                  # reads latent.g as the op above did; no alpha in it
+                g = L.LatentMixDesc()
+                g.codes, g.avg, g.styles, g.dout, g.out = _ptr(codes), _ptr(avg), _ptr(styles), _ptr(latent.g), _ptr(self.alpha_grad_rows)
+                g.R, g.J, g.D, g.backward, g.rep = R, J, D, 2, R // self.enc_rows
+                self.bwd.add(g, 'latent_mix^T.dalpha')
         self._bwd_steps.append(bwd_mix)
 
         img = self.build_stylegan(gsd, gspec, latent)

@@ -4,7 +4,8 @@ Alpha-learning objective on the fast forward path (reference: src/experiments/al
 a pre-computed adversarial set, for the three defenders.  The reference walks the set one image at a time; here `batch_images`
 images x 32 EoT rows go through the engine per call (the objective is forward-only and embarrassingly parallel over images), and
 `objective_many` scores several alpha vectors per call: the candidates and EoT replicas of an image share its encoder pass.
-`random_search` is grid_search.py:44-72; the Bayesian optimisation (bayesian_optimization.py, on the project's own Gaussian-process
+`loss_and_gradient(alphas)` is the first-order tool beside them: mean cross-entropy and its exact gradient in the alphas from one
+backward pass (gradient_descent.py).  `random_search` is grid_search.py:44-72; the Bayesian optimisation (bayesian_optimization.py, on the project's own Gaussian-process
 surrogate in gp.py instead of BoTorch) proposes `objective_many`-sized rounds.
 """
 from __future__ import annotations
@@ -82,6 +83,21 @@ class AlphaEvaluator:
     @torch.no_grad()
     def objective_function(self, alphas: Sequence[float]) -> float:
         return torch.mean(self.per_image_verdicts(alphas).to(torch.float32)).item()
+
+    def loss_and_gradient(self, alphas: Sequence[float]):
+        """(float, float64 [n]): the mean over the adversarial set of the cross-entropy of the EoT-mean logits, and its gradient in the
+        UN-attenuated vector the caller passes (the defender differentiates in its stored alphas = alphas * alpha_attenuation, so
+        its gradient is multiplied by the attenuation).  One forward and one backward pass per `batch_images` chunk
+        (EoTWrapper.loss_and_alpha_grad); fresh draws per chunk, like the objective."""
+        alphas = alphas.cpu().tolist() if isinstance(alphas, torch.Tensor) else list(alphas)
+        self.defense_model.model.interpolation_alphas = [a * self.alpha_attenuation for a in alphas]
+        loss, grad, count = 0.0, np.zeros(len(alphas), dtype=np.float64), self.images.shape[0]
+        for i in range(0, count, self.batch_images):
+            x, y = self.images[i:i + self.batch_images], self.labels[i:i + self.batch_images]
+            l, g = self.defense_model.loss_and_alpha_grad(x, y)
+            loss += float(l.double().sum())
+            grad += g.double().sum(dim=0).cpu().numpy()
+        return loss / count, grad * (self.alpha_attenuation / count)
 
     def default_candidates_per_pass(self) -> int:
         """candidates per engine pass from the row budget: ROW_BUDGET // (batch_images x EoT), at least 1"""

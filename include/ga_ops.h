@@ -231,7 +231,16 @@ typedef struct ga_sampler_desc {
                           (mu_q | logsig_q), p is [N,h,w,ldp] = (mu_p | logsig_p), ldq, ldp >= 2 NL,
                             z = 5 tanh((mu_q + mu_p)/5) + (exp(5 tanh((logsig_q + logsig_p)/5)) + 0.01) * eps;
                           backward writes dmu_q [N,h,w,ldq] and dp [N,h,w,ldp], channels [0, 2 NL) (the two are equal: the
-                          parameters enter as sums).  alpha, temp, q_rep unused. */
+                          parameters enter as sums).  alpha, temp, q_rep unused.
+                          2: the alpha cotangent of the mode-0 interpolation.  Neither z nor its gradients are formed; the op reduces
+                            dL/dalpha[n] = sum over (h, w, c < NL) of dz * (eps*sigma + dec_mu - enc_mu)
+                          per cotangent row n and writes that one float to z[n*alpha_ld + alpha_col] (z is the OUTPUT table here, alpha_ld
+                          its row pitch, alpha_col this op's column: the groups of a model fill the columns of one [rows, groups] table).
+                          Reads mu_q / ldq, p / ldp (or NULL), eps / eps_nchw, dz / ldz, N, h, w, NL, temp, q_rep with their mode-0
+                          backward meaning; alpha, one_minus_alpha, alpha_rows, dmu_q, dmu_q_rows and dp are not read (the expression
+                          holds no alpha).  backward must be 1.  GA_E_BADARG: act_rep > 1, dz or z NULL, alpha_col < 0,
+                          alpha_ld <= alpha_col.  One workgroup per row, fixed summation order, no atomics: a row's bits depend on
+                          its own data alone.  Channels c >= NL under the pitches are never read. */
     int _reserved;
     const float* alpha_rows;   /* mode 0, optional: per-row interpolation weights.  Row n reads the pair (alpha, one_minus_alpha) at
                                   alpha_rows[n*alpha_ld + 2*alpha_col + {0, 1}] instead of the scalar fields (both numbers are stored, as
@@ -333,7 +342,10 @@ int ga_pixelnorm(const float* x, float* y, long rows, int C, void* stream);
  *   backward: dcodes[r, j, :] = (1 - alpha[j]) * dout[r, j, :]
  * styles / out / dout: [R, J, D]; codes / dcodes: [R / max(rep, 1), J, D]; avg: [J, D] or NULL; alpha: [J] (device).  D % 4 == 0.
  * alpha_ld > 0: alpha is a per-row table [R][alpha_ld], alpha_ld >= J, row r uses alpha[r*alpha_ld + j]; dcodes then sums the
- * replicas' cotangents in row order, each scaled by its own (1 - alpha). */
+ * replicas' cotangents in row order, each scaled by its own (1 - alpha).
+ *   backward == 2: the alpha cotangent, out[r, j] = sum over D of dout[r, j, :] * (styles[r, j, :] - codes[r / rep, j, :] - avg[j, :]),
+ *   a dense [R, J] table through `out` (one wavefront per (r, j), fixed summation order, no atomics).  Reads dout, styles, codes, avg
+ *   (or NULL), R, J, D, rep; alpha, alpha_ld and dcodes are not read. */
 typedef struct ga_latent_mix_desc {
     const float* codes; const float* avg; const float* styles; const float* alpha; float* out;
     const float* dout; float* dcodes; int R, J, D; int backward;
@@ -654,6 +666,8 @@ const char* ga_last_hip_error(void);
  * another one: a stale .so built from another header. */
 /* (ga_avae_desc.act_rep took over a reserved int whose 0 keeps the former meaning: layout and every existing call unchanged, so
  * the version stays.) */
+/* (ga_sampler_desc.mode == 2 is a value ga_sampler_mix refused before, and ga_latent_mix_desc.backward was only ever set to 0 or 1:
+ * a formerly refused or unused mode value changes no layout and no existing call, so the version stays.) */
 #define GA_ABI_VERSION 8
 int ga_abi_version(void);
 unsigned long ga_sizeof_op(void);
