@@ -622,7 +622,9 @@ __global__ void __launch_bounds__(256) maxpool3s2_kernel(const ga_maxpool3s2_des
             const int c4 = (int)(i % C4); long p = i / C4;
             const int w = (int)(p % d.W); p /= d.W;
             const int h = (int)(p % d.H); const int n = (int)(p / d.H);
-            const floatx4 me = ld4(d.x + (((size_t)n * d.H + h) * d.W + w) * d.C + 4 * c4);
+            // K cotangents per forward row (act_rep = K): the windows are re-scanned in the forward's x, row n / K
+            const int na = d.act_rep > 1 ? n / d.act_rep : n;
+            const floatx4 me = ld4(d.x + (((size_t)na * d.H + h) * d.W + w) * d.C + 4 * c4);
             floatx4 g = {0.f, 0.f, 0.f, 0.f};
             const int ho0 = max(0, h / 2), ho1 = min(Ho - 1, (h + 1) / 2);                 // windows with 2ho-1 <= h <= 2ho+1
             const int wo0 = max(0, w / 2), wo1 = min(Wo - 1, (w + 1) / 2);
@@ -638,7 +640,7 @@ __global__ void __launch_bounds__(256) maxpool3s2_kernel(const ga_maxpool3s2_des
                         for (int kw = 0; kw < 3; ++kw) {
                             const int ww = 2 * wo - 1 + kw;
                             if (ww < 0 || ww >= d.W || (hh == h && ww == w)) continue;
-                            const floatx4 v = ld4(d.x + (((size_t)n * d.H + hh) * d.W + ww) * d.C + 4 * c4);
+                            const floatx4 v = ld4(d.x + (((size_t)na * d.H + hh) * d.W + ww) * d.C + 4 * c4);
                             const bool earlier = hh < h || (hh == h && ww < w);
 #pragma unroll
                             for (int e = 0; e < 4; ++e)
@@ -997,7 +999,9 @@ __global__ void __launch_bounds__(256) gconv_kernel(const ga_gconv_desc d, const
         }
         const size_t o = (((size_t)n * d.Ho + ho) * d.Wo + wo) * d.C + co;
         if (d.dact_x) {
-            const floatx4 u = ld4(d.dact_x + o);
+            // K cotangents per saved activation (dact_rep = K): the act' source is the forward's tensor, row n / K
+            const size_t od = d.dact_rep > 1 ? ((((size_t)(n / d.dact_rep) * d.Ho + ho) * d.Wo + wo) * d.C + co) : o;
+            const floatx4 u = ld4(d.dact_x + od);
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc[e] *= act_bwd_fast(u[e], d.dact_act);
         }
@@ -1023,6 +1027,8 @@ __global__ void __launch_bounds__(256) gconv_group_kernel(const ga_gconv_desc d,
     const int wo = (int)(p % d.Wo); long q = p / d.Wo;
     const int ho = (int)(q % d.Ho); const int n = (int)(q / d.Ho);
     const size_t ob = (size_t)p * d.C + g * CG;
+    // K cotangents per saved activation (dact_rep = K): the act' source is the forward's tensor, row n / K
+    const size_t od = d.dact_rep > 1 ? ((((size_t)(n / d.dact_rep) * d.Ho + ho) * d.Wo + wo) * d.C + g * CG) : ob;
 #pragma unroll 1
     for (int o0 = 0; o0 < CG; o0 += OB) {
         float acc[OB];
@@ -1055,7 +1061,7 @@ __global__ void __launch_bounds__(256) gconv_group_kernel(const ga_gconv_desc d,
         for (int o = 0; o < OB; o += 4) {
             floatx4 r = {acc[o], acc[o + 1], acc[o + 2], acc[o + 3]};
             if (d.dact_x) {
-                const floatx4 u = ld4(d.dact_x + ob + o0 + o);
+                const floatx4 u = ld4(d.dact_x + od + o0 + o);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) r[e] *= act_bwd_fast(u[e], d.dact_act);
             }
@@ -1091,9 +1097,10 @@ __global__ void __launch_bounds__(256) avgpool_act_kernel(const ga_avgpool_act_d
         }
     } else if (c < d.C) {
         const floatx4 g = ld4(d.dy + (size_t)n * d.C + c) * inv;
+        const int na = d.act_rep > 1 ? n / d.act_rep : n;       // K cotangents per forward row (act_rep = K): x is the forward's, row n / K
         for (int p = pl; p < d.P; p += 16) {
             const size_t o = ((size_t)n * d.P + p) * d.C + c;
-            const floatx4 v = ld4(d.x + o);
+            const floatx4 v = ld4(d.x + ((size_t)na * d.P + p) * d.C + c);
             floatx4 r;
 #pragma unroll
             for (int e = 0; e < 4; ++e) r[e] = g[e] * act_bwd(v[e], d.act);
@@ -1438,6 +1445,7 @@ extern "C" int ga_maxpool3s2(const ga_maxpool3s2_desc* d, void* s) {
     if (((d->H | d->W) & 1) || (d->C % 4)) return GA_E_UNSUPPORTED;
     if (!d->backward && !d->y) return GA_E_BADARG;
     if (d->backward && (!d->dy || !d->dx)) return GA_E_BADARG;
+    if (d->act_rep > 1 && (!d->backward || d->N % d->act_rep)) return GA_E_BADARG;
     const long total4 = d->backward ? (long)d->N * d->H * d->W * (d->C / 4) : (long)d->N * (d->H / 2) * (d->W / 2) * (d->C / 4);
     hipLaunchKernelGGL(maxpool3s2_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)s, *d, total4);
     return check_launch();
@@ -1561,6 +1569,7 @@ extern "C" int ga_gconv(const ga_gconv_desc* d, void* s) {
     ga::clear_stale_error();
     if (!d || !d->x || !d->w || !d->y || d->N <= 0 || d->Hi <= 0 || d->Wi <= 0 || d->Ho <= 0 || d->Wo <= 0) return GA_E_BADARG;
     if (d->C <= 0 || d->cg <= 0 || d->C % d->cg || d->KH <= 0 || d->KW <= 0 || d->stride <= 0 || d->pad < 0) return GA_E_BADARG;
+    if (d->dact_x && d->dact_rep > 1 && d->N % d->dact_rep) return GA_E_BADARG;
     if (d->cg % 4) return GA_E_UNSUPPORTED;
     if (!aligned16(d->x) || !aligned16(d->w) || !aligned16(d->y) || (d->bias && !aligned16(d->bias)) ||
         (d->dact_x && !aligned16(d->dact_x))) return GA_E_ALIGN;
@@ -1587,6 +1596,7 @@ extern "C" int ga_avgpool_act(const ga_avgpool_act_desc* d, void* s) {
     if (d->C % 4) return GA_E_UNSUPPORTED;
     if (!d->backward && !d->y) return GA_E_BADARG;
     if (d->backward && (!d->dy || !d->dx)) return GA_E_BADARG;
+    if (d->act_rep > 1 && (!d->backward || d->N % d->act_rep)) return GA_E_BADARG;
     const int nchunks = (d->C + 63) / 64;
     hipLaunchKernelGGL(avgpool_act_kernel, dim3(d->N * nchunks), dim3(256), 0, (hipStream_t)s, *d, nchunks);
     return check_launch();

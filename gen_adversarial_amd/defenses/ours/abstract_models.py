@@ -202,7 +202,8 @@ class _EngineOwner:
             eng.noise.copy_(snap[1][0])
             eng.noise_coef.copy_(snap[1][1])
 
-    # owners whose _make_engine takes cot_rep: the VGG classifier and, in front of it, the NVAE, ND-VAE, A-VAE and noise / blur defenders
+    # owners whose _make_engine takes cot_rep: the VGG classifier and, in front of it, the NVAE, ND-VAE, A-VAE and noise / blur
+    # defenders; the bare ResNet-50 / ResNeXt-50 classifiers
     supports_class_jacobian = False
 
     def _n_classes(self):
@@ -271,8 +272,9 @@ class BaseClassificationModel(ABC, _EngineOwner):
 
     @property
     def supports_class_jacobian(self) -> bool:
+        from ...resnet_spec import ResNetSpec
         from ...vgg_spec import VggSpec
-        return isinstance(self.classifier.spec, VggSpec)
+        return isinstance(self.classifier.spec, (VggSpec, ResNetSpec))
 
     def _make_engine(self, rows: int, rep: int, with_noise: bool = True, cot_rep: int = 1) -> Engine:
         w = self.classifier

@@ -115,9 +115,12 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
         self.share_encoder = bool(share_encoder) and rep > 1 and self.noise_eps == 0.0 and nvae_sd is not None
         self.enc_rows = rows // rep if self.share_encoder else rows
         self.need_backward = need_backward
-        if cot_rep < 1 or (cot_rep > 1 and not (self.has_nvae or isinstance(vgg_spec, VggSpec))):
-            raise ValueError('cot_rep > 1 (K-cotangent backward) is built for the defenders in front of a VGG classifier and for the '
-                             'VGG classifier itself')
+        if cot_rep < 1:
+            raise ValueError('cot_rep (cotangents per forward row of the backward plan) must be at least 1')
+        if cot_rep > 1 and not (isinstance(vgg_spec, VggSpec) or (isinstance(vgg_spec, ResNetSpec) and not self.has_nvae)):
+            raise ValueError('cot_rep > 1 (K-cotangent backward) is built for the defenders in front of a VGG classifier, for the VGG '
+                             'classifier itself and for a bare ResNet / ResNeXt classifier (input noise and blur included); still '
+                             'refused: a purifier in front of a ResNet / ResNeXt classifier, and the e4e classifier spec')
         self.cot_rep = int(cot_rep)
         self._init_alpha_grad(alpha_grad)
         self.bytes = 0
@@ -302,6 +305,9 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
         d.x, d.w, d.bias, d.dact_x, d.y = _ptr(x), _ptr(w), _ptr(bias), _ptr(dact_x), _ptr(y)
         d.N, d.Hi, d.Wi, d.Ho, d.Wo, d.C, d.cg = n, hi, wi, ho, wo, c, cg
         d.KH, d.KW, d.stride, d.pad, d.pro_act, d.dact_act = KH, KW, stride, pad, pro_act, dact_act
+        if dact_x is not None and dact_x.shape[0] != n:     # K cotangent rows per saved activation row (K-cotangent backward plan)
+            assert dact_x.shape[0] * self.cot_rep == n, (name, tuple(dact_x.shape), tuple(x.shape), self.cot_rep)
+            d.dact_rep = self.cot_rep
         plan.add(d, name)
         return d
 

@@ -102,7 +102,9 @@ class ClassifierBuilder:
 
         def bwd_stem():
             b = L.Maxpool3s2Desc()
-            b.x, b.dy, b.dx, b.N, b.H, b.W, b.C, b.backward = _ptr(c1.t), _ptr(p1.g), _ptr(c1.g), R, c1.h, c1.w, c1.c, 1
+            b.x, b.dy, b.dx, b.N, b.H, b.W, b.C, b.backward = _ptr(c1.t), _ptr(p1.g), _ptr(c1.g), R * self.cot_rep, c1.h, c1.w, c1.c, 1
+            if self.cot_rep > 1:                            # K cotangent rows re-scan the windows of one saved c1 row
+                b.act_rep = self.cot_rep
             self.bwd.add(b, 'resnet.maxpool^T')
             c1.g_written = True
             self.grad_conv('resnet.conv1^T', c1.g, stem['w_bwd'], img, K=4, pad=1, explicit_out=True,
@@ -130,8 +132,10 @@ class ClassifierBuilder:
             self.grad_conv('resnet.fc3^T', out.g, head['w_o_bwd'], h1, K=1, dact_x=h1.t, dact_act=L.GA_ACT_RELU)
             self.grad_conv('resnet.fc0^T', h1.g, head['w_h_bwd'], pooled, K=1)
             b = L.AvgpoolActDesc()
-            b.x, b.dy, b.dx, b.N, b.P, b.C, b.act, b.backward = (_ptr(last.t), _ptr(pooled.g), _ptr(last.g), R, last.h * last.w,
-                                                                 last.c, L.GA_ACT_RELU, 1)
+            b.x, b.dy, b.dx, b.N, b.P, b.C, b.act, b.backward = (_ptr(last.t), _ptr(pooled.g), _ptr(last.g), R * self.cot_rep,
+                                                                 last.h * last.w, last.c, L.GA_ACT_RELU, 1)
+            if self.cot_rep > 1:
+                b.act_rep = self.cot_rep
             assert not last.g_written
             self.bwd.add(b, 'resnet.avgpool^T')
             last.g_written = True

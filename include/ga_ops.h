@@ -288,7 +288,9 @@ typedef struct ga_gconv_desc {
     int N, Hi, Wi, Ho, Wo, C, cg;
     int KH, KW, stride, pad;
     int pro_act, dact_act;
-    int _reserved;
+    int dact_rep;             /* > 1: dact_x has N/dact_rep rows, output row n reads dact_x row n / dact_rep (K cotangents per saved
+                                 forward activation, as ga_conv_desc.dact_rep); x, w, the tap loop and the summation order are
+                                 untouched.  N % dact_rep != 0 with dact_x given: GA_E_BADARG */
 } ga_gconv_desc;
 int ga_gconv(const ga_gconv_desc* d, void* stream);
 
@@ -509,13 +511,18 @@ int ga_prelu(const ga_prelu_desc* d, void* stream);
  * deterministic, no atomics. */
 typedef struct ga_maxpool3s2_desc {
     const float* x; float* y; const float* dy; float* dx; int N, H, W, C; int backward;
+    int act_rep;      /* backward, > 1: N counts cotangent rows (dy, dx); x has N/act_rep rows, cotangent row n re-scans x row
+                         n / act_rep (same first-maximum rule, same scan order).  act_rep > 1 with backward == 0 or with
+                         N % act_rep != 0: GA_E_BADARG */
 } ga_maxpool3s2_desc;
 int ga_maxpool3s2(const ga_maxpool3s2_desc* d, void* stream);
 
 /* Global average pool with an activation prologue (torchvision ResNet `avgpool` after the last block's ReLU):
  * forward  y[n,c] = mean_p act(x[n,p,c]);  backward dx[n,p,c] = dy[n,c] / P * act'(x[n,p,c]).  x: [N,P,C], C % 4 == 0. */
 typedef struct ga_avgpool_act_desc {
-    const float* x; float* y; const float* dy; float* dx; int N, P, C; int act; int backward; int _reserved;
+    const float* x; float* y; const float* dy; float* dx; int N, P, C; int act; int backward;
+    int act_rep;      /* backward, > 1: N counts cotangent rows (dy, dx); x has N/act_rep rows, cotangent row n reads x row
+                         n / act_rep.  act_rep > 1 with backward == 0 or with N % act_rep != 0: GA_E_BADARG */
 } ga_avgpool_act_desc;
 int ga_avgpool_act(const ga_avgpool_act_desc* d, void* stream);
 
@@ -666,6 +673,10 @@ const char* ga_last_hip_error(void);
  * another one: a stale .so built from another header. */
 /* (ga_avae_desc.act_rep took over a reserved int whose 0 keeps the former meaning: layout and every existing call unchanged, so
  * the version stays.) */
+/* (ga_avgpool_act_desc.act_rep and ga_gconv_desc.dact_rep took over reserved ints in the same way, and ga_maxpool3s2_desc.act_rep
+ * took the four bytes of tail padding behind `backward` — the struct was 52 bytes padded to 56 — which every caller that zero-fills
+ * its descriptor already passed as 0: no offset moves, sizeof(ga_op) is unchanged, 0 and 1 keep the former meaning, so the version
+ * stays.) */
 /* (ga_sampler_desc.mode == 2 is a value ga_sampler_mix refused before, and ga_latent_mix_desc.backward was only ever set to 0 or 1:
  * a formerly refused or unused mode value changes no layout and no existing call, so the version stays.) */
 #define GA_ABI_VERSION 8
