@@ -453,6 +453,239 @@ def latent_mix_bwd(dout, alpha, rep=1):
     return (1 - alpha.view(1, -1, 1)) * acc
 
 
+# ---------------------------------------------------------------------------------------------------- ga_attn
+def split_heads(t, heads):
+    """[N,T,E] -> [N,heads,T,dh]: head h = channels [h*dh, (h+1)*dh)"""
+    N, T, E = t.shape
+    return t.reshape(N, T, heads, E // heads).permute(0, 2, 1, 3)
+
+
+def merge_heads(t):
+    N, h, T, dh = t.shape
+    return t.permute(0, 2, 1, 3).reshape(N, T, h * dh)
+
+
+def weighted_rows(w, m):
+    """[.., Tq, Tk] x [.., Tk, dh] -> [.., Tq, dh] = sum_key w[q][key] * m[key]"""
+    return w @ m
+
+
+def weighted_rows_in_groups(w, m):
+    """the same sum in the order csrc/attention.hip documents for P V and dS K: G = 256 / (dh / 4) key groups, group g adds its
+    keys g, g + G, ... one after the other, then the groups' partial sums are added in group order.  A yardstick for the long
+    sums only (the dtype is still the caller's)."""
+    Tk, dh = m.shape[-2], m.shape[-1]
+    G = 256 // (dh // 4)
+    steps = -(-Tk // G)
+    wp, mp = F.pad(w, (0, steps * G - Tk)), F.pad(m, (0, 0, 0, steps * G - Tk))
+    part = torch.zeros(*w.shape[:-1], G, dh, dtype=w.dtype)
+    for s in range(steps):
+        part = part + wp[..., s * G:(s + 1) * G, None] * mp[..., None, s * G:(s + 1) * G, :]
+    acc = part[..., 0, :]
+    for gg in range(1, G):
+        acc = acc + part[..., gg, :]
+    return acc
+
+
+def attn(q, k, v, heads, scale, rows=weighted_rows):
+    """q [N,Tq,E], k, v [N,Tk,E] -> out [N,Tq,E], p [N,heads,Tq,Tk] = softmax over the keys of scale * q_h k_h^T"""
+    qh, kh, vh = split_heads(q, heads), split_heads(k, heads), split_heads(v, heads)
+    s = scale * (qh @ kh.transpose(-1, -2))
+    e = torch.exp(s - s.max(dim=-1, keepdim=True).values)
+    p = e / e.sum(dim=-1, keepdim=True)
+    return merge_heads(rows(p, vh)), p
+
+
+def attn_bwd(q, k, v, heads, scale, dout, rows=weighted_rows):
+    """-> dq [N,Tq,E], dk, dv [N,Tk,E]:  dV = P^T dO, dP = dO V^T, dS = P (dP - sum_key dP P), dK = scale dS^T Q, dQ = scale dS K"""
+    qh, kh, vh, do = split_heads(q, heads), split_heads(k, heads), split_heads(v, heads), split_heads(dout, heads)
+    p = attn(q, k, v, heads, scale)[1]
+    dv = p.transpose(-1, -2) @ do
+    dp = do @ vh.transpose(-1, -2)
+    ds = p * (dp - (dp * p).sum(dim=-1, keepdim=True))
+    dk = scale * (ds.transpose(-1, -2) @ qh)
+    dq = scale * rows(ds, kh)
+    return merge_heads(dq), merge_heads(dk), merge_heads(dv)
+
+
+# ---------------------------------------------------------------------------------------------------- ga_layernorm
+def layernorm(a, b, gamma, beta, eps):
+    """x = a (+ b), [rows, C] -> y, stats [rows, 2] = (mean, rstd); biased variance, eps inside the root"""
+    x = a if b is None else a + b
+    mean = x.mean(dim=-1, keepdim=True)
+    rstd = 1 / torch.sqrt(((x - mean) ** 2).mean(dim=-1, keepdim=True) + eps)
+    return (x - mean) * rstd * gamma + beta, torch.cat([mean, rstd], dim=-1)
+
+
+def layernorm_bwd(a, b, gamma, eps, dy):
+    """d loss / d x, the same for both summands"""
+    x = a if b is None else a + b
+    mean = x.mean(dim=-1, keepdim=True)
+    rstd = 1 / torch.sqrt(((x - mean) ** 2).mean(dim=-1, keepdim=True) + eps)
+    xhat, gy = (x - mean) * rstd, dy * gamma
+    return rstd * (gy - gy.mean(dim=-1, keepdim=True) - xhat * (gy * xhat).mean(dim=-1, keepdim=True))
+
+
+# ---------------------------------------------------------------------------------------------------- ga_resize2_crop
+def _up2_axis(x, dim):
+    """bilinear x2, align_corners=False, along one axis: out[2j] = 1/4 x[j-1] + 3/4 x[j], out[2j+1] = 3/4 x[j] + 1/4 x[j+1],
+    indices clamped to the image"""
+    n = x.shape[dim]
+    j = torch.arange(n)
+    prev, nxt = x.index_select(dim, (j - 1).clamp(min=0)), x.index_select(dim, (j + 1).clamp(max=n - 1))
+    return torch.stack([0.25 * prev + 0.75 * x, 0.75 * x + 0.25 * nxt], dim=dim + 1).flatten(dim, dim + 1)
+
+
+def _up2_axis_adjoint(dy, dim):
+    n = dy.shape[dim] // 2
+    j = torch.arange(n)
+    ev, od = dy.index_select(dim, 2 * j), dy.index_select(dim, 2 * j + 1)
+    dx = 0.75 * ev + 0.75 * od
+    dx = dx.index_add(dim, (j - 1).clamp(min=0), 0.25 * ev)
+    return dx.index_add(dim, (j + 1).clamp(max=n - 1), 0.25 * od)
+
+
+def resize2_crop(x, crop):
+    """x [N,H,W,C] -> [N, 2H - 2 crop, 2W, C]: rows [crop, 2H - crop) of the x2 image"""
+    y = _up2_axis(_up2_axis(x, 1), 2)
+    return y[:, crop:y.shape[1] - crop]
+
+
+def resize2_crop_adjoint(dy, crop):
+    """dy [N, 2H - 2 crop, 2W, C] -> dx [N,H,W,C]"""
+    full = F.pad(dy, (0, 0, 0, 0, crop, crop))
+    return _up2_axis_adjoint(_up2_axis_adjoint(full, 2), 1)
+
+
+# ---------------------------------------------------------------------------------------------------- ga_gconv
+def _taps_range(n_out, n_in, stride, pad, k):
+    """the outputs o whose tap k lies inside the image (0 <= o * stride - pad + k < n_in): a range, and its first input"""
+    o = [i for i in range(n_out) if 0 <= i * stride - pad + k < n_in]
+    return (o[0], o[-1] + 1, o[0] * stride - pad + k) if o else (0, 0, 0)
+
+
+def gconv(x, w, bias, cg, KH, KW, stride, pad, Ho, Wo, pro_act=NONE, dact_x=None, dact_act=NONE, dact_rep=1):
+    """x [N,Hi,Wi,C], w [C][KH*KW*cg] with k = (kh*KW + kw)*cg + ci (row co of group g reads input channels g*cg + ci)
+    -> y [N,Ho,Wo,C] = (bias + sum over the taps inside the image) * act'(dact_x row n // dact_rep)"""
+    N, Hi, Wi, C = x.shape
+    G = C // cg
+    a = act(x, pro_act)
+    wv = w.reshape(G, cg, KH * KW, cg)                                   # [group][co][tap][ci]
+    y = torch.zeros(N, Ho, Wo, C, dtype=x.dtype)
+    if bias is not None:
+        y = y + bias
+    for kh in range(KH):
+        h0, h1, hi = _taps_range(Ho, Hi, stride, pad, kh)
+        for kw in range(KW):
+            w0, w1, wi = _taps_range(Wo, Wi, stride, pad, kw)
+            if h1 == h0 or w1 == w0:
+                continue
+            src = a[:, hi:hi + (h1 - h0 - 1) * stride + 1:stride, wi:wi + (w1 - w0 - 1) * stride + 1:stride]
+            src = src.reshape(N, h1 - h0, w1 - w0, G, 1, cg)
+            y[:, h0:h1, w0:w1] += (src * wv[:, :, kh * KW + kw]).sum(dim=-1).reshape(N, h1 - h0, w1 - w0, C)
+    if dact_x is not None:
+        y = y * dact(rep_rows(dact_x, dact_rep), dact_act)
+    return y
+
+
+# ---------------------------------------------------------------------------------------------------- ga_gauss_blur
+def _reflect(t, n):
+    """'reflect' border (no edge repeat): -1 -> 1, n -> n - 2"""
+    t = t.abs()
+    return torch.where(t >= n, 2 * (n - 1) - t, t)
+
+
+def _blur_radius(k, radius):
+    return radius if 0 < radius < k // 2 else k // 2
+
+
+def _blur_axis(x, taps, dim, radius):
+    """out[i] = sum_q taps[q] * x[reflect(i + q - k/2)], the taps within `radius` of the centre, in tap order"""
+    k, n = taps.numel(), x.shape[dim]
+    p, r, i = k // 2, _blur_radius(k, radius), torch.arange(n)
+    acc = torch.zeros_like(x)
+    for q in range(p - r, p + r + 1):
+        acc = acc + taps[q] * x.index_select(dim, _reflect(i + q - p, n))
+    return acc
+
+
+def _blur_axis_adjoint(dy, taps, dim, radius):
+    k, n = taps.numel(), dy.shape[dim]
+    p, r, i = k // 2, _blur_radius(k, radius), torch.arange(n)
+    acc = torch.zeros_like(dy)
+    for q in range(p - r, p + r + 1):
+        acc = acc.index_add(dim, _reflect(i + q - p, n), taps[q] * dy)
+    return acc
+
+
+def gauss_blur(x, taps, radius=0):
+    """x [planes,H,W]: along x, then along y (kornia's separable order)"""
+    return _blur_axis(_blur_axis(x, taps, 2, radius), taps, 1, radius)
+
+
+def gauss_blur_adjoint(dy, taps, radius=0):
+    return _blur_axis_adjoint(_blur_axis_adjoint(dy, taps, 1, radius), taps, 2, radius)
+
+
+# ---------------------------------------------------------------------------------------------------- ga_rowchan_reduce
+def pixel_sum(v):
+    return v.sum(dim=1)
+
+
+def lane_sum(v, lanes, tree):
+    """sum over dim 1 of [N,P,C] in the order csrc/elementwise.hip documents: `lanes` pixel lanes, lane l adds its pixels l,
+    l + lanes, ... one after the other; then the lanes are added as a halving tree (two-stage kernel) or in lane order (single
+    stage).  A yardstick for the long sums only."""
+    N, P, C = v.shape
+    steps = -(-P // lanes)
+    vp = F.pad(v, (0, 0, 0, steps * lanes - P)).reshape(N, steps, lanes, C)
+    part = torch.zeros(N, lanes, C, dtype=v.dtype)
+    for s in range(steps):
+        part = part + vp[:, s]
+    if tree:
+        while lanes > 1:
+            lanes //= 2
+            part = part[:, :lanes] + part[:, lanes:2 * lanes]
+        return part[:, 0]
+    acc = part[:, 0]
+    for l in range(1, lanes):
+        acc = acc + part[:, l]
+    return acc
+
+
+def segment_sum(v, S, lanes):
+    """two-stage order: S segments of ceil(P / S) pixels, each by lane_sum with the tree, then added in segment order"""
+    P = v.shape[1]
+    seg = -(-P // S)
+    acc = torch.zeros(v.shape[0], v.shape[2], dtype=v.dtype)
+    for s in range(S):
+        acc = acc + lane_sum(v[:, s * seg:min(P, (s + 1) * seg)], lanes, True)
+    return acc
+
+
+def rowchan_reduce(a, b, scale, gate=None, skip=None, a_src=None, a_w=None, total=pixel_sum):
+    """out[n,c] = scale * sum_p a[n,p,c] * (b or 1); scaled[n,p,c] = a * gate[n,c] (+ skip) when gate is given, else None.
+    a None: a[n,p,c] = sum_{k<4} a_w[c][k] * a_src[n,p,k]"""
+    if a is None:
+        a = (a_src[:, :, None, :] * a_w).sum(dim=-1)
+    out = total(a if b is None else a * b) * scale
+    if gate is None:
+        return out, None
+    scaled = a * gate[:, None, :]
+    return out, scaled if skip is None else scaled + skip
+
+
+# ---------------------------------------------------------------------------------------------------- ga_avgpool_act
+def avgpool_act(x, a):
+    """x [N,P,C] -> [N,C] = mean_p act(x)"""
+    return act(x, a).mean(dim=1)
+
+
+def avgpool_act_bwd(x, a, dy, act_rep=1):
+    P = x.shape[1]
+    return dy[:, None, :] / P * dact(rep_rows(x, act_rep), a)
+
+
 # ---------------------------------------------------------------------------------------------------- layouts
 def pitched(t, ld, fill):
     """dense [..., C] -> [..., ld] with the pad channels set to `fill`"""

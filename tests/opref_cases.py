@@ -1,8 +1,9 @@
 """
 Seeded inputs of the op-level edge tests that contain a kink (ReLU / LeakyReLU / PReLU at 0, clamp bounds, max-pool ties).
-tests/test_ops_edges_gpu.py runs the kernels on them; tests/test_opref_cpu.py asserts, with the float64 reference alone, that
-no more than opref.KINK_CAP of each case's decisions lie within opref.KINK_REL of a tie, so the share a GPU test may leave out
-of a gradient comparison is bounded before any kernel runs.  All tensors are fp32 CPU tensors.
+tests/test_ops_edges_gpu.py and tests/test_ops_edges2_gpu.py run the kernels on them; tests/test_opref_cpu.py asserts, with
+the float64 reference alone, that no more than opref.KINK_CAP of each case's decisions lie within opref.KINK_REL of a tie, so
+the share a GPU test may leave out of a gradient comparison is bounded before any kernel runs.  All tensors are fp32 CPU
+tensors.
 """
 import torch
 
@@ -85,9 +86,35 @@ def modout_case(P=35):
     return dict(t=g(N, P, C, seed=1), scale=1.0 + 0.2 * g(N, C, seed=2), add=g(P, C, seed=3), dout=g(N, P, C, seed=4))
 
 
+GCONV_WINDOWS = [(1, 1), (1, 2), (2, 1), (2, 2)]
+GCONV_ANCHORED_CG = [4, 12]
+
+
+def gconv_anchored_case(cg, KH, KW):
+    """ga_gconv as a sub-kernel of a stride-2 transpose: window anchored at the output pixel (pad 0, Ho = Hi), G = 3 groups,
+    N = 6 cotangent rows of 9 x 11 pixels (594 pixels: the third workgroup is ragged) on 2 rows of the ReLU' source"""
+    K, N, H, W, G = 3, 6, 9, 11, 3
+    C = G * cg
+    return dict(K=K, N=N, H=H, W=W, G=G, C=C, x=g(N, H, W, C, seed=1), w=g(C, KH * KW * cg, seed=2, scale=(KH * KW * cg) ** -0.5),
+                dact_x=g(N // K, H, W, C, seed=3))
+
+
+AVGPOOL_SHAPES = [(1, 4), (15, 72), (49, 132)]
+
+
+def avgpool_case(P, C):
+    N = 3
+    return dict(x=g(N, P, C, seed=1), dy=g(N, C, seed=2))
+
+
 def kink_sites():
     """(name, pre-activation in float64, kink positions) of every seeded case above"""
     out = []
+    for cg in GCONV_ANCHORED_CG:
+        for KH, KW in GCONV_WINDOWS:
+            out.append((f'gconv act\' cg={cg} {KH}x{KW}', R.f64(gconv_anchored_case(cg, KH, KW)['dact_x']), (0.0,)))
+    for P, C in AVGPOOL_SHAPES:
+        out.append((f'avgpool_act act\' P={P} C={C}', R.f64(avgpool_case(P, C)['x']), (0.0,)))
     s = se_case()
     t, w1, b1 = R.f64(s['t'], s['w1'], s['b1'])
     out.append(('se_excite hid', t.mean(dim=1) @ w1.t() + b1, (0.0,)))

@@ -1,8 +1,13 @@
 """
 tests/opref.py validated without a GPU: every backward reference equals torch.autograd.grad of its forward reference in
 float64 to 1e-12 (replicas written as repeat_interleave), the adjoint ops satisfy <A x, y> = <x, A^T y>, the layout helpers
-round-trip, and the seeded inputs of tests/test_ops_edges_gpu.py keep the share of near-tie decisions under the cap that
-test is allowed to exclude.
+round-trip, and the seeded inputs of tests/test_ops_edges_gpu.py and tests/test_ops_edges2_gpu.py keep the share of near-tie
+decisions under the cap those tests are allowed to exclude.  The references of the second sweep are checked against an
+independent formulation each: attention against autograd through torch.softmax, LayerNorm against F.layer_norm, the resize
+against F.interpolate(align_corners=False), the grouped conv against F.conv2d(groups=...) and, as its own backward, against
+autograd through it (stride 1: folding.grouped_bwd_weights; stride 2: the four anchored windows of
+folding.grouped_subpixel_weights), the blur against F.pad(mode='reflect') + F.conv2d, the reductions against .sum; adjoints
+come from autograd.
 """
 import pytest
 import torch
@@ -229,6 +234,141 @@ def test_avae_pixelnorm_sample_prelu_modout_latent_mix_unary():
     up[:, :, ::2, ::2] = lo.permute(0, 3, 1, 2)
     want = torch.nn.functional.conv2d(torch.nn.functional.pad(up, (2, 1, 2, 1)), k2.flip(0, 1).view(1, 1, 4, 4).expand(4, 1, 4, 4), groups=4)
     same(R.up2_blur(lo), want.permute(0, 2, 3, 1), 'up2_blur = upfirdn2d(up 2, pad (2, 1))')
+
+
+@pytest.mark.parametrize('dh,heads,Tk,qscale', [(16, 3, 5, 1.0), (48, 1, 257, 1.0), (112, 3, 300, 1.0), (80, 3, 300, 30.0), (128, 1, 1, 1.0)])
+def test_attn_against_autograd_through_softmax(dh, heads, Tk, qscale):
+    N, Tq, E = 2, 16, heads * dh
+    q, k, v, dout = d(N, Tq, E, seed=1) * qscale, d(N, Tk, E, seed=2), d(N, Tk, E, seed=3), d(N, Tq, E, seed=4)
+    scale = dh ** -0.5
+    qr, kr, vr = (t.clone().requires_grad_(True) for t in (q, k, v))
+    sc = scale * torch.einsum('nqhc,nkhc->nhqk', qr.view(N, Tq, heads, dh), kr.view(N, Tk, heads, dh))
+    pr = torch.softmax(sc, dim=-1)
+    want = torch.einsum('nhqk,nkhc->nqhc', pr, vr.view(N, Tk, heads, dh)).reshape(N, Tq, E)
+    out, p = R.attn(q, k, v, heads, scale)
+    same(out, want.detach(), 'attn out')
+    same(p, pr.detach(), 'attn p')
+    for got, ref, what in zip(R.attn_bwd(q, k, v, heads, scale, dout), grad(want, dout, qr, kr, vr), ('dq', 'dk', 'dv')):
+        same(got, ref, f'attn {what}')
+    # the kernel-order yardstick is the same sum
+    same(R.attn(q, k, v, heads, scale, rows=R.weighted_rows_in_groups)[0], out, 'attn out, group order')
+    same(R.attn_bwd(q, k, v, heads, scale, dout, rows=R.weighted_rows_in_groups)[0], R.attn_bwd(q, k, v, heads, scale, dout)[0], 'dq, group order')
+    if qscale > 1:
+        assert float((sc.detach().amax(dim=-1) - sc.detach().amin(dim=-1)).min()) > 30 and float(sc.detach().abs().max()) > 89   # expf overflows
+    if Tk == 1:
+        assert bool((p == 1).all()) and torch.equal(out, v.expand(N, Tq, E))
+
+
+@pytest.mark.parametrize('C', [4, 100, 260, 1028])
+@pytest.mark.parametrize('with_b', [True, False])
+def test_layernorm_against_f_layer_norm(C, with_b):
+    rows, eps = 7, 1e-5
+    a, b, gamma, beta, dy = d(rows, C, seed=1), (d(rows, C, seed=2) if with_b else None), d(C, seed=3), d(C, seed=4), d(rows, C, seed=5)
+    a = a + 100.0 * d(rows, 1, seed=6)
+    ar = a.clone().requires_grad_(True)
+    x = ar if b is None else ar + b
+    want = torch.nn.functional.layer_norm(x, (C,), gamma, beta, eps)
+    y, stats = R.layernorm(a, b, gamma, beta, eps)
+    same(y, want.detach(), 'layernorm')
+    same(stats[:, 0], x.detach().mean(dim=-1))
+    same(stats[:, 1], (x.detach().var(dim=-1, unbiased=False) + eps) ** -0.5)
+    same(R.layernorm_bwd(a, b, gamma, eps, dy), grad(want, dy, ar)[0], 'layernorm backward')
+
+
+@pytest.mark.parametrize('H,W,crop', [(1, 1, 0), (5, 7, 0), (5, 7, 1), (6, 10, 3), (8, 8, 0)])
+def test_resize2_crop_against_interpolate(H, W, crop):
+    N, C = 3, 4
+    x, dy = d(N, H, W, C, seed=1), d(N, 2 * H - 2 * crop, 2 * W, C, seed=2)
+    xr = x.clone().requires_grad_(True)
+    up = torch.nn.functional.interpolate(xr.permute(0, 3, 1, 2), scale_factor=2, mode='bilinear', align_corners=False)
+    want = up[:, :, crop:2 * H - crop].permute(0, 2, 3, 1)
+    same(R.resize2_crop(x, crop), want.detach(), 'resize2_crop')
+    same(R.resize2_crop_adjoint(dy, crop), grad(want, dy, xr)[0], 'resize2_crop adjoint')
+
+
+def _torch_w(w, cg, KH, KW):
+    """ga_gconv layout [C][(kh*KW + kw)*cg + ci] -> [C, cg, KH, KW]"""
+    return w.view(w.shape[0], KH, KW, cg).permute(0, 3, 1, 2).contiguous()
+
+
+@pytest.mark.parametrize('cg', [4, 12])
+@pytest.mark.parametrize('stride', [1, 2])
+def test_gconv_against_grouped_conv2d(cg, stride):
+    from gen_adversarial_amd.folding import conv_fwd_layout, grouped_bwd_weights, grouped_subpixel_weights
+    N, G, H, W = 2, 3, 9 if stride == 1 else 6, 11 if stride == 1 else 10
+    C = G * cg
+    Ho, Wo = (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
+    x, w, b = d(N, H, W, C, seed=1), d(C, 9 * cg, seed=2, scale=0.2).float().double(), d(C, seed=3)   # folding returns fp32 weights
+    xr = x.clone().requires_grad_(True)
+    wt = _torch_w(w, cg, 3, 3)
+    want = torch.nn.functional.conv2d(torch.relu(xr).permute(0, 3, 1, 2), wt, b, stride=stride, padding=1, groups=G).permute(0, 2, 3, 1)
+    same(R.gconv(x, w, b, cg, 3, 3, stride, 1, Ho, Wo, pro_act=R.RELU), want.detach(), 'gconv forward')
+    same(R.gconv(x, w, None, cg, 3, 3, stride, 1, Ho, Wo), torch.nn.functional.conv2d(x.permute(0, 3, 1, 2), wt, None, stride=stride, padding=1,
+                                                                                       groups=G).permute(0, 2, 3, 1), 'no bias, no act')
+    K = 3                                                               # K cotangents per forward row
+    cot = d(N * K, Ho, Wo, C, seed=4)
+    xk = R.rep_rows(x, K).requires_grad_(True)
+    yk = torch.nn.functional.conv2d(torch.relu(xk).permute(0, 3, 1, 2), wt, b, stride=stride, padding=1, groups=G).permute(0, 2, 3, 1)
+    (gx,) = grad(yk, cot, xk)
+    if stride == 1:                                                     # its own backward-to-input: swapped, flipped weights and act'
+        wb = conv_fwd_layout(grouped_bwd_weights(wt, G))
+        same(R.gconv(cot, wb, None, cg, 3, 3, 1, 1, H, W, dact_x=x, dact_act=R.RELU, dact_rep=K), gx, 'gconv backward')
+    else:                                                               # the transpose as four anchored windows, one per output parity
+        sub = grouped_subpixel_weights(wt, G)
+        assert sorted((kh, kw) for _, kh, kw in sub.values()) == [(1, 1), (1, 2), (2, 1), (2, 2)]
+        dense = torch.zeros(N * K, H, W, C, dtype=torch.float64)
+        for (pa, pb), (wab, kh, kw) in sub.items():
+            dense[:, pa::2, pb::2] = R.gconv(cot, wab, None, cg, kh, kw, 1, 0, Ho, Wo, dact_x=x[:, pa::2, pb::2], dact_act=R.RELU, dact_rep=K)
+        same(dense, gx, 'stride-2 transpose from anchored sub-kernels')
+
+
+@pytest.mark.parametrize('H,W,k,radius', [(8, 12, 15, 0), (12, 8, 15, 0), (5, 90, 9, 0), (12, 40, 23, 0), (12, 40, 23, 4)])
+def test_gauss_blur_against_reflect_pad_and_conv2d(H, W, k, radius):
+    x, dy = d(3, H, W, seed=1), d(3, H, W, seed=2)
+    taps = torch.exp(-(torch.arange(k, dtype=torch.float64) - k // 2) ** 2 / 2)
+    taps = taps / taps.sum()
+    used = taps.clone()
+    if radius:
+        used[:k // 2 - radius] = 0
+        used[k // 2 + radius + 1:] = 0
+    xr = x.clone().requires_grad_(True)
+    p = k // 2
+    y = torch.nn.functional.pad(xr[:, None], (p, p, p, p), mode='reflect')
+    y = torch.nn.functional.conv2d(torch.nn.functional.conv2d(y, used.view(1, 1, 1, k)), used.view(1, 1, k, 1))[:, 0]
+    same(R.gauss_blur(x, taps, radius), y.detach(), 'blur')
+    same(R.gauss_blur_adjoint(dy, taps, radius), grad(y, dy, xr)[0], 'blur adjoint')
+    if radius:                                                          # the skipped taps lie below the resolution of the result
+        assert (R.gauss_blur(x, taps, radius) - R.gauss_blur(x, taps)).abs().max().item() < 1e-3
+
+
+def test_rowchan_reduce_and_its_summation_orders():
+    N, P, C = 2, 4100, 20
+    a, b, gate, skip = d(N, P, C, seed=1), d(N, P, C, seed=2), d(N, C, seed=3), d(N, P, C, seed=4)
+    out, scaled = R.rowchan_reduce(a, b, 0.5, gate, skip)
+    same(out, 0.5 * (a * b).sum(dim=1))
+    same(scaled, a * gate[:, None] + skip)
+    assert R.rowchan_reduce(a, None, 1.0)[1] is None
+    same(R.rowchan_reduce(a, None, 1.0)[0], a.sum(dim=1))
+    src, aw = d(N, P, 4, seed=5), d(C, 4, seed=6)
+    same(R.rowchan_reduce(None, b, 1.0, a_src=src, a_w=aw)[0], (torch.einsum('npk,ck->npc', src, aw) * b).sum(dim=1))
+    for S, lanes in ((2, 32), (5, 64), (3, 16)):
+        same(R.segment_sum(a, S, lanes), a.sum(dim=1), 'segment order')
+    same(R.lane_sum(a[:, :4095], 16, False), a[:, :4095].sum(dim=1), 'lane order')
+
+
+@pytest.mark.parametrize('P,C', CS.AVGPOOL_SHAPES)
+@pytest.mark.parametrize('a', [R.NONE, R.RELU, R.SILU])
+def test_avgpool_act(P, C, a):
+    c = CS.avgpool_case(P, C)
+    x, dy = R.f64(c['x'], c['dy'])
+    K = 3
+    xr = x.clone().requires_grad_(True)
+    f = {R.NONE: lambda u: u, R.RELU: torch.relu, R.SILU: torch.nn.functional.silu}[a]
+    want = f(xr).mean(dim=1)
+    same(R.avgpool_act(x, a), want.detach(), 'avgpool_act')
+    (gx,) = grad(want, dy, xr)
+    same(R.avgpool_act_bwd(x, a, dy), gx, 'avgpool_act backward')
+    same(R.avgpool_act_bwd(x, a, R.rep_rows(dy, K), act_rep=K), R.rep_rows(gx, K), 'act_rep')
 
 
 def test_seeded_gpu_inputs_stay_under_the_kink_cap():

@@ -696,11 +696,28 @@ def _cap_pixelnorm():
     return y, R.pixelnorm(R.f64(x)), R.pixelnorm(x)
 
 
+def _cap_resize2_crop():
+    N, H, W = 1, 2, 262177                              # output quads = 4 * 2 W = CAP + 264 (attention.hip's grid_for2: 8192 workgroups too)
+    x = g(N, H, W, 4, seed=1)
+    y = Out(N, 2 * H, 2 * W, 4)
+    launch(L.Resize2CropDesc, x=dev(x), y=y, N=N, H=H, W=W, C=4, crop=0)
+    return y, R.resize2_crop(R.f64(x), 0), R.resize2_crop(x, 0)
+
+
+def _cap_gconv_generic():
+    Wi, cg = 699137, 12                                 # cg = 12 has no LDS-weights kernel; pixels * 3 quads = CAP + 259
+    x, w, b = g(1, 1, Wi, cg, seed=1), g(cg, cg, seed=2, scale=0.3), g(cg, seed=3)
+    y = Out(1, 1, Wi, cg)
+    launch(L.GconvDesc, x=dev(x), w=dev(w), bias=dev(b), y=y, N=1, Hi=1, Wi=Wi, Ho=1, Wo=Wi, C=cg, cg=cg, KH=1, KW=1, stride=1, pad=0)
+    x64, w64, b64 = R.f64(x, w, b)
+    return y, x64 @ w64.t() + b64, x @ w.t() + b        # one group, one tap: a 12 x 12 matrix per pixel
+
+
 CAPPED = dict(se_apply=_cap_se_apply, bilinear_up2_bwd=_cap_bilinear, sampler_mix=_cap_sampler, maxpool2=_cap_maxpool2,
               maxpool3s2=_cap_maxpool3s2, unary=_cap_unary, modout=_cap_modout, up2_blur=_cap_up2_blur, latent_mix=_cap_latent_mix,
               pool_denorm=_cap_pool_denorm, prelu=_cap_prelu, image_io=_cap_image_io, interleave2=_cap_interleave2,
               rep_sum=_cap_rep_sum, axpby=_cap_axpby, avae_avgpool=_cap_avae_avgpool, avae_sample=_cap_avae_sample,
-              pixelnorm=_cap_pixelnorm)
+              pixelnorm=_cap_pixelnorm, resize2_crop=_cap_resize2_crop, gconv_generic=_cap_gconv_generic)
 
 
 @pytest.mark.parametrize('op', list(CAPPED))
@@ -708,7 +725,9 @@ def test_second_trip_of_the_capped_grid(op):
     """every entry point whose grid is capped at 8192 workgroups (ga_pixelnorm: 65535) with 8192 * 256 + 257 work items, or
     the nearest its shape rules allow, at its narrowest channel count: the grid-stride loop takes a second, partial trip.
     The WHOLE output is compared: exactly where the op is a selection, a copy or one rounded operation (the builder returns
-    no fp32 result), else by the new-op rule."""
+    no fp32 result), else by the new-op rule.  resize2_crop's grid comes from attention.hip's own capping helper (8192 workgroups
+    as well): fp32-CPU err / bound / kernel err 4.1e-7 / 1.6e-6 / 3.5e-7; gconv_generic is ga_gconv's grid-stride kernel (cg = 12, one
+    tap): 1.1e-6 / 4.4e-6 / 8.0e-7."""
     out, ref, fp32 = CAPPED[op]()
     got = out.done()
     if fp32 is None:

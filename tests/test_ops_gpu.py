@@ -8,6 +8,8 @@ Entry points and fields that are not tested here:
                                 ga_axpby, ga_pool_denorm, interleaved ga_modout, shared-alpha ga_latent_mix, ga_sampler_mix
                                 mode 1, the replica fields act_rep / dact_rep / cot_rep, odd and non-square images, and the
                                 second trip of every capped grid
+  tests/test_ops_edges2_gpu.py  against the same references: ga_attn, ga_layernorm, ga_resize2_crop, ga_gconv, ga_gauss_blur,
+                                ga_rowchan_reduce and ga_avgpool_act at the shapes the tests below leave out
   tests/test_plan_convs_gpu.py  every tuned convolution of the shipped plans against tests/convref.py
   tests/test_dec_cell_gpu.py, tests/test_dec_cell_halo_gpu.py       ga_dec_cell, ga_dec_cell_halo
   tests/test_alpha_search_gpu.py                                    per-row alpha tables of ga_sampler_mix / ga_latent_mix
