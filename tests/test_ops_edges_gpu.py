@@ -253,7 +253,9 @@ def test_image_io_cot_rep(s2d):
 @pytest.mark.parametrize('N,H,Cc,Hd,variant', [(6, 8, 256, 64, 0), (6, 16, 128, 32, 1)])
 def test_dec_cell_backward_act_rep(N, H, Cc, Hd, variant):
     """ga_dec_cell backward with 3 cotangents per forward row against the plain-PyTorch cell of test_dec_cell_gpu.py through
-    autograd, at that file's tolerance (2e-4; kernel err 4.9e-6 and 4.5e-6 of 1.05)"""
+    autograd, at that file's tolerance (2e-4; kernel err 4.9e-6 and 4.5e-6 of 1.05), and row by row against the float64 cell of
+    tests/cellref.py within cellref.row_bound (emulation err / bound / kernel err: 4.8e-6 / 1.9e-5 / 4.9e-6 and 4.6e-6 / 1.8e-5 /
+    4.5e-6; kernel / emulation of the worst row 1.03 and 1.05)"""
     from test_dec_cell_gpu import _cell, _split, _torch_cell
     K = 3
     assert L.lib.ga_dec_cell_supported(N, H, H, Cc, Hd) == 1
@@ -273,6 +275,12 @@ def test_dec_cell_backward_act_rep(N, H, Cc, Hd, variant):
     assert torch.isfinite(out).all()
     print(f'dec_cell act_rep: kernel err {R.max_err(out.permute(0, 3, 1, 2), gt1):.3e} of {gt1.abs().max().item():.3e}')
     close(out.permute(0, 3, 1, 2), gt1, 2e-4, 'dec_cell backward, act_rep = 3')
+    # and row by row against float64, within 4 x the error of the split-bf16 emulation (tests/cellref.py)
+    import cellref as CR
+    args = [t.contiguous() for t in (x.permute(0, 2, 3, 1), w1[:, :, 0, 0], b1, wd.reshape(Hd, 25).t(), bd, w2[:, :, 0, 0], b2,
+                                     dout.permute(0, 2, 3, 1), ps, pb)]
+    CR.check_rows('dec_cell backward, act_rep = 3', out, CR.emulate_backward(*args, act_rep=K),
+                  CR.cell_backward(*R.f64(*args), act_rep=K))
 
 
 @pytest.mark.parametrize('K', [1, 3])

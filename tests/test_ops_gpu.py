@@ -11,7 +11,10 @@ Entry points and fields that are not tested here:
   tests/test_ops_edges2_gpu.py  against the same references: ga_attn, ga_layernorm, ga_resize2_crop, ga_gconv, ga_gauss_blur,
                                 ga_rowchan_reduce and ga_avgpool_act at the shapes the tests below leave out
   tests/test_plan_convs_gpu.py  every tuned convolution of the shipped plans against tests/convref.py
-  tests/test_dec_cell_gpu.py, tests/test_dec_cell_halo_gpu.py       ga_dec_cell, ga_dec_cell_halo
+  tests/test_dec_cell_gpu.py, tests/test_dec_cell_halo_gpu.py       ga_dec_cell, ga_dec_cell_halo against fp32 PyTorch
+  tests/test_dec_cell_f64_gpu.py, tests/test_dec_cell_halo_f64_gpu.py   the same two row by row against the float64 cell of
+                                tests/cellref.py: every accepted geometry, the chunk pipeline, act_rep, aliased addends,
+                                bit equality with the unfused launches, refusals
   tests/test_alpha_search_gpu.py                                    per-row alpha tables of ga_sampler_mix / ga_latent_mix
   tests/test_stylegan_gpu.py, tests/test_trans_gpu.py, tests/test_resnet_gpu.py   ga_up2_blur, ga_attn, ga_layernorm,
                                 ga_resize2_crop and the remaining pieces inside their models
