@@ -94,6 +94,13 @@ def se_excite_fwd(m, w1, b1, w2, b2):
     return hid, torch.sigmoid(act(hid, RELU) @ w2.t() + b2)
 
 
+def se_excite_bwd(dgate, hid, gate, w1, w2, res_scale, P):
+    """the unfused backward: dgate [N,C] (already d / d gate) -> pro_scale = res_scale * gate, pro_shift = d m / P"""
+    ds = dgate * gate * (1 - gate)
+    dh = (ds @ w2) * (hid > 0).to(ds.dtype)
+    return res_scale * gate, (dh @ w1) / P
+
+
 def se_excite_bwd_fused(t, dout, hid, gate, w1, w2, res_scale, act_rep=1):
     """t [N/K,P,C], dout [N,P,C] -> pro_scale, pro_shift [N,C]: d t = dout * pro_scale + pro_shift"""
     tr, hr, gr = rep_rows(t, act_rep), rep_rows(hid, act_rep), rep_rows(gate, act_rep)
@@ -148,6 +155,33 @@ def sampler_nd_bwd(mu_q, p, eps, dz, act_rep=1):
     dmu = dz * (1 - torch.tanh(ms / 5) ** 2)
     dls = dz * eps * torch.exp(_sc5(ls)) * (1 - torch.tanh(ls / 5) ** 2)
     return torch.cat([dmu, dls], dim=-1)
+
+
+# ---------------------------------------------------------------------------------------------------- ga_sampler_mix, mode 0
+def sampler_mix(mu_q, mu_p, logsig_p, eps, alpha, one_minus_alpha, temp):
+    """z = (1 - alpha) enc_mu + alpha (eps * sigma + dec_mu); all [N,h,w,NL], rows already expanded; mu_p None: the prior N(0, 1)
+    of the first group (logsig_p is then zeros).  alpha / one_minus_alpha: floats or [N,1,1,1]"""
+    mp = torch.zeros_like(mu_q) if mu_p is None else mu_p
+    sigma = temp * torch.exp(_sc5(logsig_p))
+    return one_minus_alpha * _sc5(mp + mu_q) + alpha * (eps * sigma + _sc5(mp))
+
+
+def sampler_mix_bwd(mu_q, mu_p, logsig_p, eps, dz, alpha, one_minus_alpha, temp):
+    """-> d mu_q, d mu_p, d logsig_p, each [N,h,w,NL] per (cotangent) row; mu_p None as in sampler_mix"""
+    mp = torch.zeros_like(mu_q) if mu_p is None else mu_p
+    sech2 = lambda v: 1 - torch.tanh(v / 5) ** 2
+    denc = one_minus_alpha * dz * sech2(mp + mu_q)
+    dmp = denc + alpha * dz * sech2(mp)
+    dls = alpha * dz * eps * temp * torch.exp(_sc5(logsig_p)) * sech2(logsig_p)
+    return denc, dmp, dls
+
+
+# ---------------------------------------------------------------------------------------------------- ga_sampler_mix, mode 2
+def sampler_alpha_terms(mu_q, mu_p, logsig_p, eps, dz, temp):
+    """the terms of d loss / d alpha: dz * (eps * sigma + dec_mu - enc_mu), [N,h,w,NL], operands as in sampler_mix; row n's
+    cotangent of alpha is their sum"""
+    mp = torch.zeros_like(mu_q) if mu_p is None else mu_p
+    return dz * (eps * (temp * torch.exp(_sc5(logsig_p))) + _sc5(mp) - _sc5(mp + mu_q))
 
 
 # ---------------------------------------------------------------------------------------------------- ga_dml_mean
@@ -453,6 +487,45 @@ def latent_mix_bwd(dout, alpha, rep=1):
     return (1 - alpha.view(1, -1, 1)) * acc
 
 
+def latent_mix_rows(codes, avg, styles, alpha, rep=1):
+    """the alpha_ld form: alpha [R,J], row r mixes with its own alpha[r]"""
+    c = rep_rows(codes, rep)
+    if avg is not None:
+        c = c + avg
+    a = alpha[:, :, None]
+    return (1 - a) * c + a * styles
+
+
+def latent_mix_rows_bwd(dout, alpha, rep=1):
+    """dcodes sums the replicas' cotangents in row order, each scaled by its own (1 - alpha)"""
+    R, J, D = dout.shape
+    rep = max(rep, 1)
+    v = ((1 - alpha[:, :, None]) * dout).reshape(R // rep, rep, J, D)
+    acc = v[:, 0].clone()
+    for r in range(1, rep):
+        acc = acc + v[:, r]
+    return acc
+
+
+def latent_alpha_terms(codes, avg, styles, dout, rep=1):
+    """backward 2: the terms of d loss / d alpha, dout * (styles - (codes + avg)), [R,J,D]; out[r][j] is their sum over D"""
+    c = rep_rows(codes, rep)
+    return dout * (styles - (c if avg is None else c + avg))
+
+
+def sampler_alpha_c(T):
+    """ga_sampler_mix mode 2: additions on the longest path of the kernel's summation tree over T terms -- ceil(T / 256) into a
+    thread's strided partial sum, 6 steps of the wave-64 butterfly, 3 for the four waves' partials added in wave order -- plus 16
+    for the rounding of one term (two tanhf, one expf, the products): |err| <= c * 2^-24 * sum |term|"""
+    return -(-T // 256) + 6 + 3 + 16
+
+
+def latent_alpha_c(D):
+    """ga_latent_mix backward 2: a lane adds 4 per quad it owns (three inside the quad, one into its sum), ceil(D / 4 / 64) quads,
+    then 6 butterfly steps; plus 3 for the rounding of one term (codes + avg, styles - that, the product)"""
+    return 4 * -(-(D // 4) // 64) + 6 + 3
+
+
 # ---------------------------------------------------------------------------------------------------- ga_attn
 def split_heads(t, heads):
     """[N,T,E] -> [N,heads,T,dh]: head h = channels [h*dh, (h+1)*dh)"""
@@ -661,6 +734,25 @@ def segment_sum(v, S, lanes):
     for s in range(S):
         acc = acc + lane_sum(v[:, s * seg:min(P, (s + 1) * seg)], lanes, True)
     return acc
+
+
+def reduce_order(N, P, C, ws_floats):
+    """(segments S, pixel lanes) of a ga_rowchan_reduce launch as include/ga_ops.h and the kernels' comments give them: two
+    stages when a workspace is given and P >= 4096, S = ws_floats / (N C) capped at 2048 workgroups and at 1024 pixels per
+    segment, ql = the power of two >= min(16, C / 4) channel-quad lanes x 256 / ql pixel lanes; S < 2: one stage, 16 pixel lanes"""
+    nchunks = (C + 63) // 64
+    S = min(ws_floats // (N * C), 2048 // (N * nchunks), (P + 1023) // 1024) if ws_floats and P >= 4096 else 1
+    if S < 2:
+        return 1, 16
+    ql = 1
+    while ql < min(16, C // 4):
+        ql *= 2
+    return S, 256 // ql
+
+
+def order_sum(S, lanes):
+    """the `total` of rowchan_reduce in that order"""
+    return (lambda v: segment_sum(v, S, lanes)) if S > 1 else (lambda v: lane_sum(v, lanes, False))
 
 
 def rowchan_reduce(a, b, scale, gate=None, skip=None, a_src=None, a_w=None, total=pixel_sum):

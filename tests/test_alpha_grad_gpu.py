@@ -20,6 +20,7 @@ if not torch.cuda.is_available():
     pytest.skip('needs a GPU', allow_module_level=True)
 
 from gen_adversarial_amd import _lib as L   # noqa: E402
+import opref   # noqa: E402
 from alpha_grad_cases import LABELS, REFERENCES   # noqa: E402
 from alpha_search_cases import B, CASES, E   # noqa: E402
 
@@ -47,10 +48,8 @@ ALPHA_LD, ALPHA_COL = 5, 3
 
 
 def sampler_c(T):
-    """additions on the longest path of sampler_alpha_grad_kernel's summation tree: ceil(T / 256) into a thread's strided partial sum
-    (csrc/elementwise.hip: `for (i = threadIdx.x; i < T; i += 256) acc += ...`), 6 __shfl_xor steps of the wave-64 butterfly, 3 for the
-    four waves' partials added in wave order by thread 0; plus 16 for the rounding of one term (two tanhf, one expf, the products)"""
-    return -(-T // 256) + 6 + 3 + 16
+    """additions on the longest path of sampler_alpha_grad_kernel's summation tree (tests/opref.py holds the count)"""
+    return opref.sampler_alpha_c(T)
 
 
 def sampler_data(case, seed):
@@ -64,15 +63,14 @@ def sampler_data(case, seed):
 
 
 def sampler_terms64(case, mq, p, eps, dz, temp):
-    """the header's formula on the float32 inputs in float64: [N, h * w * NL] terms"""
+    """the header's formula (tests/opref.py) on the float32 inputs in float64: [N, h * w * NL] terms"""
     N, q_rep, h, NL, _, ldp = case
-    mq64 = np.repeat(mq.astype(np.float64), q_rep, axis=0)
-    mp = np.zeros_like(mq64) if p is None else p[..., :NL].astype(np.float64)
-    ls = np.zeros_like(mq64) if p is None else p[..., NL:].astype(np.float64)
-    sc = lambda v: 5.0 * np.tanh(v / 5.0)
-    e64 = eps.astype(np.float64).transpose(0, 2, 3, 1)
-    term = dz.astype(np.float64) * (e64 * (temp * np.exp(sc(ls))) + sc(mp) - sc(mp + mq64))
-    return term.reshape(N, -1)
+    t64 = lambda v: torch.from_numpy(np.ascontiguousarray(v)).double()
+    mq64 = opref.rep_rows(t64(mq), q_rep)
+    mp = None if p is None else t64(p[..., :NL])
+    ls = torch.zeros_like(mq64) if p is None else t64(p[..., NL:])
+    term = opref.sampler_alpha_terms(mq64, mp, ls, t64(eps).permute(0, 2, 3, 1), t64(dz), temp)
+    return term.reshape(N, -1).numpy()
 
 
 def sampler_desc(case, mq_d, p_d, eps_d, dz_d, table, eps_nchw, temp, N=None, q_rep=None):
@@ -143,9 +141,8 @@ def test_sampler_alpha_cotangent_refusals():
 
 # ---------------------------------------------------------------------------------------------------------------- latent mix, backward 2
 def latent_c(D):
-    """additions on the longest path of latent_alpha_grad_kernel: a lane adds 4 per quad it owns (three inside the quad, one into its
-    sum), ceil(D / 4 / 64) quads, then 6 __shfl_xor steps; plus 3 for the rounding of one term (codes + avg, styles - that, the product)"""
-    return 4 * -(-(D // 4) // 64) + 6 + 3
+    """additions on the longest path of latent_alpha_grad_kernel (tests/opref.py holds the count)"""
+    return opref.latent_alpha_c(D)
 
 
 @pytest.mark.parametrize('with_avg', [False, True])
@@ -157,8 +154,8 @@ def test_latent_alpha_cotangent_against_float64(shape, with_avg):
     avg = rng.randn(J, D).astype(np.float32) if with_avg else None
     styles = rng.randn(R, J, D).astype(np.float32)
     dout = rng.randn(R, J, D).astype(np.float32)
-    ca = np.repeat(codes.astype(np.float64), rep, axis=0) + (avg.astype(np.float64) if with_avg else 0.0)
-    terms = dout.astype(np.float64) * (styles.astype(np.float64) - ca)
+    t64 = lambda v: None if v is None else torch.from_numpy(v).double()
+    terms = opref.latent_alpha_terms(t64(codes), t64(avg), t64(styles), t64(dout), rep).numpy()
     ref, mag, c = terms.sum(axis=2), np.abs(terms).sum(axis=2), latent_c(D)
     cd, sd, dd = dev(codes), dev(styles), dev(dout)
     ad = dev(avg) if with_avg else None

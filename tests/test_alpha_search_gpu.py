@@ -17,6 +17,7 @@ if not torch.cuda.is_available():
     pytest.skip('needs a GPU', allow_module_level=True)
 
 from gen_adversarial_amd import _lib as L   # noqa: E402
+import opref   # noqa: E402
 from alpha_search_cases import B, CASES, E, K, candidate_rows   # noqa: E402
 
 DEV = 'cuda:0'
@@ -44,19 +45,15 @@ def test_sampler_with_per_row_alphas(first):
     alpha = rng.rand(N, ncol)
     alpha[0, col], alpha[1, col] = 0.0, 1.0
     table = np.stack([alpha.astype(np.float32), (1.0 - alpha).astype(np.float32)], axis=2).reshape(N, 2 * ncol)
-    # float64 reference on the float32 inputs, with the pair the kernel reads
-    a, om = (table[:, 2 * col + i].astype(np.float64).reshape(N, 1, 1, 1) for i in (0, 1))
-    mq64 = np.repeat(mq.astype(np.float64), q_rep, axis=0)
-    mp = np.zeros_like(mq64) if first else p[..., :NL].astype(np.float64)
-    ls = np.zeros_like(mq64) if first else p[..., NL:].astype(np.float64)
-    e64 = eps.astype(np.float64).transpose(0, 2, 3, 1)
-    sc = lambda v: 5.0 * np.tanh(v / 5.0)
-    dsc = lambda v: 1.0 - np.tanh(v / 5.0) ** 2
-    sig = temp * np.exp(sc(ls))
-    z_ref = om * sc(mp + mq64) + a * (e64 * sig + sc(mp))
-    dz = cot.astype(np.float64)
-    denc = om * dz * dsc(mp + mq64)
-    dmp_ref, dls_ref = denc + a * dz * dsc(mp), a * dz * e64 * sig * dsc(ls)
+    # float64 reference (tests/opref.py) on the float32 inputs, with the pair the kernel reads
+    t64 = lambda v: torch.from_numpy(np.ascontiguousarray(v)).double()
+    a, om = (t64(table[:, 2 * col + i]).view(N, 1, 1, 1) for i in (0, 1))
+    mq64 = opref.rep_rows(t64(mq), q_rep)
+    mp = None if first else t64(p[..., :NL])
+    ls = torch.zeros_like(mq64) if first else t64(p[..., NL:])
+    e64 = t64(eps).permute(0, 2, 3, 1)
+    z_ref = opref.sampler_mix(mq64, mp, ls, e64, a, om, temp).numpy()
+    denc, dmp_ref, dls_ref = (v.numpy() for v in opref.sampler_mix_bwd(mq64, mp, ls, e64, t64(cot), a, om, temp))
 
     dev = lambda t: torch.from_numpy(np.ascontiguousarray(t)).to(DEV)
     mqd = torch.full((N // q_rep, h, h, LD), 7.0, device=DEV)
@@ -97,8 +94,9 @@ def test_sampler_with_per_row_alphas(first):
     if not first:
         d.dp = dp2.data_ptr()
     L.run(d)
-    rep2 = lambda t: np.repeat(t, Kc, axis=0)
-    _close64(rows2[..., :NL], rep2(om) * cot2.astype(np.float64) * rep2(dsc(mp + mq64)), 1e-6, 'sampler dmu_q_rows, act_rep 2')
+    rep2 = lambda t: None if t is None else opref.rep_rows(t, Kc)
+    denc2 = opref.sampler_mix_bwd(rep2(mq64), rep2(mp), rep2(ls), rep2(e64), t64(cot2), rep2(a), rep2(om), temp)[0].numpy()
+    _close64(rows2[..., :NL], denc2, 1e-6, 'sampler dmu_q_rows, act_rep 2')
 
 
 def test_latent_mix_with_per_row_alphas():
@@ -115,7 +113,8 @@ def test_latent_mix_with_per_row_alphas():
     table[0, 0], table[1, 0] = 0.0, 1.0
     a = table[:, :J].astype(np.float64).reshape(R, J, 1)
     ca = np.repeat(codes.astype(np.float64), rep, axis=0) + avg.astype(np.float64)
-    ref = (1.0 - a) * ca + a * styles.astype(np.float64)
+    t64 = lambda v: torch.from_numpy(np.ascontiguousarray(v)).double()
+    ref = opref.latent_mix_rows(t64(codes), t64(avg), t64(styles), t64(table[:, :J]), rep).numpy()
     bound = 4 * 2.0 ** -24 * (np.abs(1.0 - a) * np.abs(ca) + np.abs(a) * np.abs(styles.astype(np.float64)))
     dev = lambda t: torch.from_numpy(np.ascontiguousarray(t)).to(DEV)
     cd, ad, sd, dd, td = dev(codes), dev(avg), dev(styles), dev(dout), dev(table)
@@ -128,7 +127,7 @@ def test_latent_mix_with_per_row_alphas():
     print(f'   latent_mix fwd, per-row alphas: max err {err.max():.3e}, max err / bound {(err / np.maximum(bound, 1e-300)).max():.3f}')
     assert (err <= bound).all()
     term = (1.0 - a) * dout.astype(np.float64)
-    ref_d = term.reshape(R // rep, rep, J, D).sum(axis=1)
+    ref_d = opref.latent_mix_rows_bwd(t64(dout), t64(table[:, :J]), rep).numpy()
     bound_d = (rep + 1) * 2.0 ** -24 * np.abs(term).reshape(R // rep, rep, J, D).sum(axis=1)
     dcodes = torch.zeros(R // rep, J, D, device=DEV)
     m.backward, m.dout, m.dcodes = 1, dd.data_ptr(), dcodes.data_ptr()

@@ -89,6 +89,36 @@ def test_sampler_mode1_backward():
     same(ref, gp, 'd p')
 
 
+@pytest.mark.parametrize('first', [False, True])
+def test_sampler_mode0_backward_and_alpha_terms(first):
+    """per-row alphas; `first`: the prior N(0, 1) of the first group (mu_p None, logsig_p zeros).  The alpha cotangent of mode 2
+    is d / d alpha of the forward with one_minus_alpha = 1 - alpha"""
+    N, h, w, NL, temp = 4, 3, 5, 6, 0.6
+    mq, eps, dz = d(N, h, w, NL, seed=1, scale=3).requires_grad_(True), d(N, h, w, NL, seed=2), d(N, h, w, NL, seed=3)
+    mp = None if first else d(N, h, w, NL, seed=4, scale=3).requires_grad_(True)
+    ls = torch.zeros(N, h, w, NL, dtype=torch.float64) if first else d(N, h, w, NL, seed=5).requires_grad_(True)
+    a = torch.rand(N, 1, 1, 1, generator=torch.Generator().manual_seed(6), dtype=torch.float64).requires_grad_(True)
+    leaves = [mq, a] if first else [mq, mp, ls, a]
+    g = grad(R.sampler_mix(mq, mp, ls, eps, a, 1 - a, temp), dz, *leaves)
+    ref = R.sampler_mix_bwd(*R.f64(mq, mp, ls), eps, dz, a.detach(), 1 - a.detach(), temp)
+    same(ref[0], g[0], 'd mu_q')
+    if not first:
+        same(ref[1], g[1], 'd mu_p')
+        same(ref[2], g[2], 'd logsig_p')
+    same(R.sampler_alpha_terms(*R.f64(mq, mp, ls), eps, dz, temp).flatten(1).sum(dim=1), g[-1].flatten(), 'd alpha')
+
+
+def test_latent_mix_rows_backward_and_alpha_terms():
+    R_, rep, J, D = 6, 3, 5, 8
+    codes, avg, styles, dout = d(R_ // rep, J, D, seed=1), d(J, D, seed=2), d(R_, J, D, seed=3), d(R_, J, D, seed=4)
+    a = torch.rand(R_, J, generator=torch.Generator().manual_seed(5), dtype=torch.float64).requires_grad_(True)
+    for av in (avg, None):
+        c = codes.clone().requires_grad_(True)
+        gc_, ga = grad(R.latent_mix_rows(c, av, styles, a, rep), dout, c, a)
+        same(R.latent_mix_rows_bwd(dout, a.detach(), rep), gc_, 'd codes')
+        same(R.latent_alpha_terms(codes, av, styles, dout, rep).sum(dim=-1), ga, 'd alpha')
+
+
 def test_dml_mean_backward_and_the_oracle_forward():
     from oracle.nvae_oracle import disc_mix_logistic_mean
     c = CS.dml_case()

@@ -307,22 +307,7 @@ def test_gauss_blur_edges(H, W, k, radius):
 # =====================================================================================================================
 # ga_rowchan_reduce
 # =====================================================================================================================
-def _reduce_order(N, P, C, ws_floats):
-    """(segments S, pixel lanes) of the launch as include/ga_ops.h and the kernels' comments give them: two stages when a
-    workspace is given and P >= 4096, S = ws_floats / (N C) capped at 2048 workgroups and at 1024 pixels per segment, ql = the
-    power of two >= min(16, C / 4) channel-quad lanes x 256 / ql pixel lanes; S < 2: one stage, 16 pixel lanes"""
-    nchunks = (C + 63) // 64
-    S = min(ws_floats // (N * C), 2048 // (N * nchunks), (P + 1023) // 1024) if ws_floats and P >= 4096 else 1
-    if S < 2:
-        return 1, 16
-    ql = 1
-    while ql < min(16, C // 4):
-        ql *= 2
-    return S, 256 // ql
-
-
-def _order_sum(S, lanes):
-    return (lambda v: R.segment_sum(v, S, lanes)) if S > 1 else (lambda v: R.lane_sum(v, lanes, False))
+_reduce_order, _order_sum = R.reduce_order, R.order_sum        # the launch's summation order: tests/opref.py holds it
 
 
 def _reduce(N, P, C, a=None, b=None, ws=None, ws_floats=0, scale=0.5, **kw):

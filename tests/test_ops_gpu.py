@@ -11,6 +11,10 @@ Entry points and fields that are not tested here:
   tests/test_ops_edges2_gpu.py  against the same references: ga_attn, ga_layernorm, ga_resize2_crop, ga_gconv, ga_gauss_blur,
                                 ga_rowchan_reduce and ga_avgpool_act at the shapes the tests below leave out
   tests/test_plan_convs_gpu.py  every tuned convolution of the shipped plans against tests/convref.py
+  tests/test_plan_ops_gpu.py    every other op of the shipped plans, with the pitches, slices, aliases, replica fields and extents
+                                the engines give it, against tests/planref.py (float64 interpreter of the descriptors; checked on
+                                the CPU by tests/test_planref_cpu.py over the dry-run plans of tests/planzoo.py): the three
+                                benchmarked plans and the reduced competitor, K-cotangent and alpha engines
   tests/test_dec_cell_gpu.py, tests/test_dec_cell_halo_gpu.py       ga_dec_cell, ga_dec_cell_halo against fp32 PyTorch
   tests/test_dec_cell_f64_gpu.py, tests/test_dec_cell_halo_f64_gpu.py   the same two row by row against the float64 cell of
                                 tests/cellref.py: every accepted geometry, the chunk pipeline, act_rep, aliased addends,
