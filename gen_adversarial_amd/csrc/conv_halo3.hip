@@ -13,7 +13,6 @@
 // Wide images (Wo a multiple of 128: the 256^2 .. 1024^2 layers of the e4e encoder and the StyleGAN2 synthesis network): the
 // tile is a 128-pixel SEGMENT of one row and its window 3 x 130 pixels (3x the tile instead of 9x); 13 patch slots per thread
 // instead of 9, hence a second set of instantiations (template parameter RP).
-#include <type_traits>
 #include "conv_split.h"
 #include "conv_epilogue.h"
 
@@ -48,7 +47,7 @@ struct halo_geom {
     int TH, NI, PH, PW, P;      // rows per image in the tile, images per tile, patch rows / cols per image, patch pixels
     int TW, wide;               // tile width (= Wo, or 128 for a row segment of a wide image: wide = 1)
     int RS, IS;                 // row / image stride of a patch plane, in bf16 elements
-    int ldh;                    // pixel pitch of a patch plane, in bf16 elements (LDH; 48 for the 16x16x32 fragment reads of tile 8)
+    int ldh;                    // pixel pitch of a patch plane, in bf16 elements (LDH)
     fastdiv fd_howo, fd_wo, fd_phpw, fd_pw, fd_thwo, fd_tw, fd_is;
 };
 
@@ -308,7 +307,7 @@ static void launch_halo_inst(const ga_conv_desc& d, hipStream_t stream, dim3 gri
 // and the patch is double-buffered where it fits: ONE barrier per 32-channel chunk (9 taps, 216 MFMAs per wave) instead of nine.
 // Same operand split and accumulation order (conv_split.h: split4, mfma3) and k order as conv_halo3_kernel: bitwise the same results.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int AFF, int ACT, int RPMAX, bool M16>
+template <int AFF, int ACT, int RPMAX>
 __global__ void __launch_bounds__(256, 2)
 conv_halo3_bd_kernel(const ga_conv_desc d, const int tilesN, const int M, const int C, const int nkc, const int vec_out,
                      const halo_geom g, const int dbuf, const int tab_off) {
@@ -325,9 +324,7 @@ conv_halo3_bd_kernel(const ga_conv_desc d, const int tilesN, const int M, const 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wn = wave;
     const int c4 = tid & 7;
-    // fragment lane map: 32x32x16 -> row lane & 31, k octet lane >> 5 (of a 16-deep step); 16x16x32 -> row lane & 15, k octet
-    // lane >> 4 (of the 32-deep chunk)
-    const int lrow = M16 ? (lane & 15) : (lane & 31), lh = M16 ? (lane >> 4) : (lane >> 5);
+    const int lrow = lane & 31, lh = lane >> 5;             // fragment lane map: row, k octet (of a 16-deep step)
 
     constexpr int INV = 0x7fffffff;
     const int HoWo = d.Ho * d.Wo;
@@ -383,23 +380,14 @@ conv_halo3_bd_kernel(const ga_conv_desc d, const int tilesN, const int M, const 
     }
     // a thread's slot entries are read by itself only; the prologue table is read by everybody in the first finish_patch below
     if (AFF != 0) __syncthreads();
-    // 16x16x32: M tiles 4..7 sit 64 tile pixels behind tiles 0..3 — whole rows or whole images further, i.e. at ONE uniform
-    // offset (`halfoff`): 4 address registers serve all 8 fragments
     int fragA[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int o = i * (M16 ? 16 : 32) + lrow;
+        const int o = i * 32 + lrow;
         const int img = fd_div(o, g.fd_thwo);
         const int rem = o - img * g.TH * g.TW;
         const int y = fd_div(rem, g.fd_tw), x = rem - y * g.TW;
         fragA[i] = img * g.IS + y * g.RS + x * LDHr + 8 * lh;
-    }
-    int halfoff = 0;
-    if (M16) {
-        const int img = fd_div(64, g.fd_thwo);
-        const int rem = 64 - img * g.TH * g.TW;
-        const int y = fd_div(rem, g.fd_tw), x = rem - y * g.TW;
-        halfoff = img * g.IS + y * g.RS + x * LDHr;
     }
 
     auto issue_patch = [&](const int chunk) __attribute__((always_inline)) {
@@ -449,59 +437,31 @@ conv_halo3_bd_kernel(const ga_conv_desc d, const int tilesN, const int M, const 
         for (int q = 0; q < 4; ++q) b[q] = p[q * 64];
     };
 
-    // accumulators: 4 tiles of 32 x 32 (floatx16), or 8 x 2 tiles of 16 x 16 (floatx4) — 64 registers either way
-    typedef typename std::conditional<M16, floatx4[8][2], floatx16[TM][TN]>::type acc_t;
-    acc_t acc;
-    if constexpr (M16) {
+    floatx16 acc[TM][TN];                                    // 4 tiles of 32 x 32: 64 registers
 #pragma unroll
-        for (int i = 0; i < 8; ++i)
+    for (int i = 0; i < TM; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
-    } else {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][0][r] = 0.f;
-    }
+        for (int r = 0; r < 16; ++r) acc[i][0][r] = 0.f;
 
-    // A fragments of a group = 8 ds_read_b128 feeding 12 MFMAs of 32 cycles (32x32x16: group = (tap, k step), 4 M tiles x hi | lo)
-    // or 24 MFMAs of 16 cycles (16x16x32: group = (tap, half of the 8 M tiles), the whole 32-deep chunk per read); two register
-    // sets: the reads of group g + 1 are issued BEFORE the MFMAs of group g (the waits the compiler inserts are then counted ones:
-    // lgkmcnt(8) instead of a drain), so that a wave's instruction stream is MFMAs back to back with its operand reads riding in
-    // the gaps
-    bf16x8 ahs[M16 ? 1 : 2][4], als[M16 ? 1 : 2][4];
-    auto load_A = [&](const int set, const int buf, const int off, const int half) __attribute__((always_inline)) {
+    // A fragments of a group = 8 ds_read_b128 feeding 12 MFMAs of 32 cycles (group = (tap, k step), 4 M tiles x hi | lo); two
+    // register sets: the reads of group g + 1 are issued BEFORE the MFMAs of group g (the waits the compiler inserts are then
+    // counted ones: lgkmcnt(8) instead of a drain), so that a wave's instruction stream is MFMAs back to back with its operand
+    // reads riding in the gaps
+    bf16x8 ahs[2][4], als[2][4];
+    auto load_A = [&](const int set, const int buf, const int off) __attribute__((always_inline)) {
         const __bf16* Ph = Pbase + buf * 2 * plane;
         const __bf16* Pl = Ph + plane;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            ahs[set][i] = *reinterpret_cast<const bf16x8*>(Ph + fragA[i] + off + (M16 ? half * halfoff : 0));
-            als[set][i] = *reinterpret_cast<const bf16x8*>(Pl + fragA[i] + off + (M16 ? half * halfoff : 0));
+            ahs[set][i] = *reinterpret_cast<const bf16x8*>(Ph + fragA[i] + off);
+            als[set][i] = *reinterpret_cast<const bf16x8*>(Pl + fragA[i] + off);
         }
     };
-    // weight fragments of one tap in b[4]: 32x32x16 -> [k step][hi | lo]; 16x16x32 -> [16-channel half of the wave's 32][hi | lo]
-    auto mma_group = [&](const int set, const uintx4 (&b)[4], const int sel) __attribute__((always_inline)) {
-        if constexpr (M16) {
-            const bf16x8 bh0 = __builtin_bit_cast(bf16x8, b[0]), bl0 = __builtin_bit_cast(bf16x8, b[1]);
-            const bf16x8 bh1 = __builtin_bit_cast(bf16x8, b[2]), bl1 = __builtin_bit_cast(bf16x8, b[3]);
+    // weight fragments of one tap in b[4]: [k step][hi | lo]
+    auto mma_group = [&](const int set, const uintx4 (&b)[4], const int ks) __attribute__((always_inline)) {
+        const bf16x8 bh = __builtin_bit_cast(bf16x8, b[2 * ks]), bl = __builtin_bit_cast(bf16x8, b[2 * ks + 1]);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                floatx4& c0 = acc[4 * sel + i][0];
-                floatx4& c1 = acc[4 * sel + i][1];
-                c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(als[set][i], bh0, c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(als[set][i], bh1, c1, 0, 0, 0);
-                c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahs[set][i], bl0, c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahs[set][i], bl1, c1, 0, 0, 0);
-                c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahs[set][i], bh0, c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahs[set][i], bh1, c1, 0, 0, 0);
-            }
-        } else {
-            const bf16x8 bh = __builtin_bit_cast(bf16x8, b[2 * sel]), bl = __builtin_bit_cast(bf16x8, b[2 * sel + 1]);
-#pragma unroll
-            for (int i = 0; i < TM; ++i) mfma3(acc[i][0], ahs[set][i], als[set][i], bh, bl);
-        }
+        for (int i = 0; i < TM; ++i) mfma3(acc[i][0], ahs[set][i], als[set][i], bh, bl);
     };
 
     GA_HSTAMP(1)
@@ -515,57 +475,7 @@ conv_halo3_bd_kernel(const ga_conv_desc d, const int tilesN, const int M, const 
     int buf = 0;
     const int rowskip = g.RS - 3 * LDHr;
     for (int chunk = cb; chunk < ce; ++chunk) {
-        load_A(0, buf, 0, 0);
-        if constexpr (M16) {
-            // 16x16x32: ONE fragment register set, refilled tile by tile: the 6 MFMAs of M tile i (3 per 16-channel half of the
-            // wave's outputs) are followed by the two reads of tile i of the NEXT group into the registers they have just consumed —
-            // 18 MFMAs (288 cycles) before their first use
-            const __bf16* Ph = Pbase + buf * 2 * plane;
-            const __bf16* Pl = Ph + plane;
-#pragma unroll
-            for (int gi = 0; gi < 18; ++gi) {
-                const int tap = gi >> 1, half = gi & 1;
-                if (half == 0) {
-                    const int ntap = tap == 8 ? 0 : tap + 1;
-                    const int nchunk = tap == 8 ? min(chunk + 1, ce - 1) : chunk;
-                    load_B(bnxt, nchunk, ntap);
-                }
-                const int nt2 = (gi + 1) >> 1;
-                const int noff = nt2 * LDHr + (nt2 / 3) * rowskip + ((gi + 1) & 1) * halfoff;
-                const bf16x8 bh0 = __builtin_bit_cast(bf16x8, bcur[0]), bl0 = __builtin_bit_cast(bf16x8, bcur[1]);
-                const bf16x8 bh1 = __builtin_bit_cast(bf16x8, bcur[2]), bl1 = __builtin_bit_cast(bf16x8, bcur[3]);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    floatx4& c0 = acc[4 * half + i][0];
-                    floatx4& c1 = acc[4 * half + i][1];
-                    c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(als[0][i], bh0, c0, 0, 0, 0);
-                    c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(als[0][i], bh1, c1, 0, 0, 0);
-                    c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahs[0][i], bl0, c0, 0, 0, 0);
-                    c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahs[0][i], bl1, c1, 0, 0, 0);
-                    c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahs[0][i], bh0, c0, 0, 0, 0);
-                    c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahs[0][i], bh1, c1, 0, 0, 0);
-                    if (gi + 1 < 18) {
-                        ahs[0][i] = *reinterpret_cast<const bf16x8*>(Ph + fragA[i] + noff);
-                        als[0][i] = *reinterpret_cast<const bf16x8*>(Pl + fragA[i] + noff);
-                    }
-                }
-                __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);       // (the global loads, when this group has them)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                if (dbuf && gi == 9 && chunk + 1 < ce) {
-                    finish_patch(chunk + 1, buf ^ 1);
-                    if (chunk + 2 < ce) issue_patch(chunk + 2);
-                }
-                if (half == 1) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) bcur[q] = bnxt[q];
-                }
-            }
-        } else
+        load_A(0, buf, 0);
 #pragma unroll
         for (int gi = 0; gi < 18; ++gi) {
             const int tap = gi >> 1, ks = gi & 1;
@@ -577,13 +487,13 @@ conv_halo3_bd_kernel(const ga_conv_desc d, const int tilesN, const int M, const 
             }
             if (gi + 1 < 18) {
                 const int nt2 = (gi + 1) >> 1;
-                const int noff = nt2 * LDHr + (nt2 / 3) * rowskip + (M16 ? 0 : ((gi + 1) & 1) * 16);
-                load_A((gi + 1) & 1, buf, noff, (gi + 1) & 1);
+                const int noff = nt2 * LDHr + (nt2 / 3) * rowskip + ((gi + 1) & 1) * 16;
+                load_A((gi + 1) & 1, buf, noff);
             }
             __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);       // (the global loads, when this group has them)
             __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);       // next group's 8 fragment reads first ...
             mma_group(gi & 1, bcur, ks);
-            __builtin_amdgcn_sched_group_barrier(0x008, M16 ? 24 : 12, 0);      // ... then this group's MFMAs
+            __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);      // ... then this group's MFMAs
             __builtin_amdgcn_sched_barrier(0);
             if (dbuf && gi == 9 && chunk + 1 < ce) {        // the next chunk's patch into the other buffer, behind the MFMAs
                 finish_patch(chunk + 1, buf ^ 1);
@@ -612,12 +522,12 @@ conv_halo3_bd_kernel(const ga_conv_desc d, const int tilesN, const int M, const 
     GA_HSTAMP(4)
 }
 
-template <int AFF, int ACT, int RP, bool M16>
+template <int AFF, int ACT, int RP>
 static void launch_halo_bd_inst(const ga_conv_desc& d, hipStream_t stream, dim3 grid, size_t lds, int tilesN, int M, int nkc, int vec_out,
                                 const halo_geom& g, int dbuf, int tab_off) {
     static dyn_lds_cache attr;
-    (void)ensure_dyn_lds(attr, reinterpret_cast<const void*>(&conv_halo3_bd_kernel<AFF, ACT, RP, M16>), lds);
-    hipLaunchKernelGGL((conv_halo3_bd_kernel<AFF, ACT, RP, M16>), grid, dim3(256), lds, stream, d, tilesN, M, d.C1, nkc, vec_out, g, dbuf,
+    (void)ensure_dyn_lds(attr, reinterpret_cast<const void*>(&conv_halo3_bd_kernel<AFF, ACT, RP>), lds);
+    hipLaunchKernelGGL((conv_halo3_bd_kernel<AFF, ACT, RP>), grid, dim3(256), lds, stream, d, tilesN, M, d.C1, nkc, vec_out, g, dbuf,
                        tab_off);
 }
 
@@ -690,14 +600,13 @@ static int launch_halo(const ga_conv_desc& d, hipStream_t stream, int vec_out, i
     return check_launch();
 }
 
-template <bool M16>
-static int launch_halo_bd(const ga_conv_desc& d, hipStream_t stream, int vec_out, int splits, const int ldh) {
+static int launch_halo_bd(const ga_conv_desc& d, hipStream_t stream, int vec_out, int splits) {
     constexpr int BM = 128, BN = 128;
     if (!d.w_frag || !aligned16(d.w_frag)) return GA_E_UNSUPPORTED;
     const int M = d.N * d.Ho * d.Wo;
     const int nkc = d.C1 / HK;
     halo_geom g;
-    { const int rc = halo_geometry(d, BM, g, ldh); if (rc != GA_OK) return rc; }
+    { const int rc = halo_geometry(d, BM, g); if (rc != GA_OK) return rc; }
     if (splits > nkc) return GA_E_UNSUPPORTED;
     const int tilesM = (M + BM - 1) / BM, tilesN = (d.Cout + BN - 1) / BN;
     const size_t patch = (size_t)2 * g.NI * g.IS * 2;                   // hi + lo planes of one buffer, bytes
@@ -717,7 +626,7 @@ static int launch_halo_bd(const ga_conv_desc& d, hipStream_t stream, int vec_out
     const dim3 grid(tilesM * tilesN, splits);
     if (g.P > 9 * 32) return GA_E_UNSUPPORTED;                          // row-segment tiles of wide images: the LDS-staged kernel
 #define GA_HBD(MODE, A, C, WIDE) \
-    case MODE: launch_halo_bd_inst<A, C, 9, M16>(d, stream, grid, lds, tilesN, M, nkc, vec_out, g, dbuf, tab_off); break;
+    case MODE: launch_halo_bd_inst<A, C, 9>(d, stream, grid, lds, tilesN, M, nkc, vec_out, g, dbuf, tab_off); break;
     switch (mode) {
 #ifdef GA_HALO_EXP_ONLY     // quick experiment builds (make hexp): two prologues only
         GA_CONV3_MODES_EXP(GA_HBD)
@@ -734,16 +643,8 @@ static int launch_halo_bd(const ga_conv_desc& d, hipStream_t stream, int vec_out
 // global memory (needs w_frag); called by ga_conv2d after validation
 int conv_halo3_dispatch(const ga_conv_desc& d, hipStream_t stream, int tile, int vec_out, int splits) {
     switch (tile) {
-        case 8: return launch_halo_bd<false>(d, stream, vec_out, splits, LDH);
-#ifdef GA_HALO_EXP_ONLY
-        // experiment build only (make hexp, tools/conv_ab.py): the same kernel on v_mfma_f32_16x16x32_bf16 (M16), w_frag in the m16
-        // order (WeightStore.frag3(w, m16=True)); 9 = 80-B pixel pitch (2-way fragment reads), 10 = 96-B pitch (conflict-free).
-        // Measured r04 (gpurun_out/r04_ab_m16.log): the bare MFMA loop runs 15 % faster on this shape, the kernel
-        // 2 - 7 % (16x16x128: 111.4 -> 105.9 us, 8x8x256: 102.2 -> 100.3, 32x32x64: 213.8 -> 199.8) and 4 % SLOWER at 4x4x512
-        // (115.3 -> 120.3): not worth a second set of instantiations (+5 minutes of build) and a second weight copy — not shipped.
-        case 9: return launch_halo_bd<true>(d, stream, vec_out, splits, 40);
-        case 10: return launch_halo_bd<true>(d, stream, vec_out, splits, 48);
-#else
+        case 8: return launch_halo_bd(d, stream, vec_out, splits);
+#ifndef GA_HALO_EXP_ONLY    // (make hexp: tile 8 alone)
         case 5: return launch_halo<2, 2, 2, 2>(d, stream, vec_out, splits);
         case 6: return launch_halo<4, 1, 1, 2>(d, stream, vec_out, splits);
         case 7: return launch_halo<4, 1, 1, 1>(d, stream, vec_out, splits);

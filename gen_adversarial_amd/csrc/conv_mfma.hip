@@ -550,7 +550,7 @@ extern "C" int ga_conv2d(const ga_conv_desc* dp, void* stream_) {
     } else if (tile == 12) {            // 1x1 with the weight fragments read from global memory (explicit request only; w_frag with one tap)
         if (!(bf3 && vec_out && conv_pw_frag_supports(d, splits))) return GA_E_UNSUPPORTED;
         rc = conv_pw_frag_dispatch(k, stream, vec_out);
-    } else if (tile >= 5 && tile <= 10) {      // halo-staged 3x3 (explicit request only: the tune table names it per shape)
+    } else if (tile >= 5 && tile <= 8) { // halo-staged 3x3 (explicit request only: the tune table names it per shape)
         if (!(bf3 && vec_out && conv_halo3_supports(d))) return GA_E_UNSUPPORTED;
         rc = conv_halo3_dispatch(k, stream, tile, vec_out, splits);
     } else if (bf3) {

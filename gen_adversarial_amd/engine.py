@@ -25,8 +25,8 @@ from .nvae_spec import DecCellSpec, EncCellSpec, NVAESpec, build_spec
 from .e4e_spec import E4ESpec
 from .resnet_spec import ResNetSpec
 from .vgg_spec import VggSpec
-from .engine_core import (IMG_LD, RES_SCALE, TUNE_FILE, WS_FLOATS, Act, WeightStore, _ptr, conv_key,  # noqa: F401
-                          frag_ok, halo_ok, pw_ok, thin_ok, tune_cache)
+from .engine_core import (IMG_LD, RES_SCALE, TILES, TUNE_FILE, WS_FLOATS, Act, WeightStore, _ptr, conv_key,  # noqa: F401
+                          candidate_tiles, resolve_tile, tile_candidates, tune_cache)
 from .engine_classifiers import ClassifierBuilder
 from .engine_e4e import E4EBuilder
 from .engine_avae import AvaeBuilder
@@ -123,17 +123,7 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
                              'refused: a purifier in front of a ResNet / ResNeXt classifier, and the e4e classifier spec')
         self.cot_rep = int(cot_rep)
         self._init_alpha_grad(alpha_grad)
-        self.bytes = 0
-        self.acts = {}                       # name -> Act (debugging / tests)
-        self.version = 0                     # bumped by callers after each forward (stale-backward detection)
-        self._sampler_descs = []             # (desc, latent index): alphas can be changed without rebuilding
-        self._keep = []                      # weights etc.
-        self._frag_ok = {}                   # id(ConvDesc) -> weight tensor of the convs that may run on tile 8
-        self._thin_ok = {}                   # ... on tile 11
-        self._pw_ok = {}                     # ... on tile 12
-        self.fwd = L.Plan()
-        self.bwd = L.Plan()
-        self._bwd_steps = []                 # closures emitting backward ops, replayed in reverse
+        self._init_plans()
         self._build(nvae_sd, vgg_sd)
 
     @classmethod
@@ -167,14 +157,26 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
         self.enc_rows = rows // rep if self.share_encoder else rows
         self.need_backward, self.image_s2d, self.cot_rep = need_backward, False, int(cot_rep)
         self._init_alpha_grad(alpha_grad)
-        self.bytes, self.acts, self.version, self._sampler_descs, self._keep, self._frag_ok, self._thin_ok, self._pw_ok = 0, {}, 0, [], [], {}, {}, {}
-        self.fwd, self.bwd, self._bwd_steps, self._scratch = L.Plan(), L.Plan(), [], {}
+        self._init_plans()
+        self._scratch = {}
         self.eps, self.purified, self.dpurified, self._purified_grad_nhwc = [], None, None, None
         return self
 
     def finish(self):
         self._finish(0)
         return self
+
+    def _init_plans(self):
+        """the empty plans and what their builders fill beside them"""
+        self.bytes = 0
+        self.acts = {}                       # name -> Act (debugging / tests)
+        self.version = 0                     # bumped by callers after each forward (stale-backward detection)
+        self._sampler_descs = []             # (desc, latent index): alphas can be changed without rebuilding
+        self._keep = []                      # weights etc.
+        self._conv_w = {}                    # id(ConvDesc) -> weight tensor of every split-bf16 conv (the fragment-fed tiles' copies)
+        self.fwd = L.Plan()
+        self.bwd = L.Plan()
+        self._bwd_steps = []                 # closures emitting backward ops, replayed in reverse
 
     def _init_alpha_rows(self, alpha_rows: bool):
         self.alpha_rows, self.alpha_table = bool(alpha_rows), None
@@ -240,19 +242,10 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
         if self.precision == 'bf16x3' and not self.dry_run and not precise:
             hi, lo = self.store.split(w)
             d.w_hi, d.w_lo = _ptr(hi), _ptr(lo)
-            kh, kw = (KH or K), (KW or K)
-            if (kh, kw, sn, sd, pad) == (3, 3, 1, 1, 1) and x2 is None and (cin or x.shape[3]) % 32 == 0 and 128 % x.shape[2] == 0 \
-                    and w.dim() == 2 and w.shape[1] == 9 * (cin or x.shape[3]):
-                # tile 8 reads its B fragments from a fragment-ordered copy of the weights (WeightStore.frag3).  The copy is built
-                # LAZILY — by apply_tuning for the descs whose tuned tile is 8, by autotune for its candidates — not for every
-                # eligible 3x3 weight (52 of 1594 tuned shapes select tile 8; an eager copy doubled the split-weight memory)
-                self._frag_ok[id(d)] = w
-            if (kh, kw, sn, sd, pad) == (3, 3, 1, 1, 1) and x2 is None and (cin or x.shape[3]) in (32, 64) and x.shape[1] % 8 == 0 \
-                    and x.shape[2] % 16 == 0 and w.dim() == 2 and w.shape[1] == 9 * (cin or x.shape[3]):
-                self._thin_ok[id(d)] = w                    # tile 11 (conv_thin3): persistent weights-resident kernel, its own fragment order
-            if (kh, kw, sn, sd, pad) == (1, 1, 1, 1, 0) and x2 is None and (cin or x.shape[3]) % 16 == 0 \
-                    and w.numel() == (cout or y.shape[3]) * (cin or x.shape[3]):
-                self._pw_ok[id(d)] = w                      # tile 12 (conv_pw_frag): the one-tap fragment order, built lazily like tile 8's
+            # tiles 8, 11 and 12 read fragment-ordered copies of the weights (engine_core.TILES).  A copy is built LAZILY — by
+            # apply_tuning for the descs whose tuned tile reads it, by autotune for its candidates — not for every eligible weight
+            # (52 of 1594 tuned shapes select tile 8; an eager copy doubled the split-weight memory)
+            self._conv_w[id(d)] = w
         d.pro_scale, d.pro_shift, d.pro_act, d.pro_per_row = _ptr(pro_scale), _ptr(pro_shift), pro_act, pro_per_row
         No, Ho, Wo, Cy = y.shape
         d.y, d.ldy = _ptr(y), (ldy or Cy)
@@ -540,45 +533,30 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
                 tile, splits = 0, 1
             if not use_bf3:                      # this shape is faster on the exact fp32 kernel (small K or Cout)
                 d.w_hi, d.w_lo = None, None
-            # conv_key does not encode pad / Wo / the weight layout: a desc can share the key of a tile-8 or tile-11 entry without
-            # being eligible for that tile.  It then runs tile 5 (8) or 7 (11), which give the same bits, when the halo kernel
-            # takes it, else the library heuristic
-            if tile == 8 and not (self._want_frag(d) and frag_ok(d, splits)):
-                tile = 5
-            if tile == 11 and (splits > 1 or not (self._want_thin(d) and thin_ok(d, splits))):
-                tile, splits = 7, 1
-            if tile in (5, 6, 7) and not halo_ok(d, tile, splits):
-                tile, splits = 0, 1
-            if tile == 12 and (splits > 1 or not (self._want_pw(d) and pw_ok(d, splits))):
-                tile, splits = 0, 1                 # (tile 12 gives the bits of tiles 1 - 4)
+            tile, splits = resolve_tile(d, tile, splits, lambda t: self._want(d, t))
             d.tile, d.splits = int(tile), int(splits)
             d.ws, d.ws_floats = (_ptr(self.ws), WS_FLOATS) if splits > 1 else (None, 0)
         self.fwd.finalize()
         self.bwd.finalize()
 
-    def _want_frag(self, d) -> bool:
-        """point d.w_frag at the tile-8 fragment copy (built on first use); False when this conv cannot run on tile 8"""
-        w = self._frag_ok.get(id(d))
-        if w is None or self.dry_run:
+    def _frag_weight(self, d, tile):
+        """the weight tensor of d when the fragment copy of `tile` can be made of it, else None"""
+        w = self._conv_w.get(id(d))
+        return w if w is not None and not self.dry_run and TILES[tile].weight_ok(d, w) else None
+
+    def _want(self, d, tile) -> bool:
+        """point d.w_frag at the fragment copy of d's weights that `tile` reads (built on first use); False when there is none"""
+        w = self._frag_weight(d, tile)
+        if w is None:
             return False
-        d.w_frag = _ptr(self.store.frag3(w))
+        d.w_frag = _ptr(TILES[tile].frag(self.store, w, d))
         return True
 
-    def _want_thin(self, d) -> bool:
-        """point d.w_frag at the tile-11 fragment copy; False when this conv cannot run on tile 11"""
-        w = self._thin_ok.get(id(d))
-        if w is None or self.dry_run:
-            return False
-        d.w_frag = _ptr(self.store.frag_thin(w))
-        return True
-
-    def _want_pw(self, d) -> bool:
-        """point d.w_frag at the one-tap fragment copy of a 1x1 conv's weights (built on first use); False when it cannot run on tile 12"""
-        w = self._pw_ok.get(id(d))
-        if w is None or self.dry_run:
-            return False
-        d.w_frag = _ptr(self.store.frag3(w.reshape(d.Cout, d.C1), taps=1))
-        return True
+    def candidate_keys(self, tile) -> list:
+        """the tune-table keys of the convs for which autotune times `tile` (tools/tune.py retune)"""
+        keys = [conv_key(d) for d in self._conv_descs()
+                if tile in candidate_tiles(d, lambda t: self._frag_weight(d, t) is not None)]
+        return list(dict.fromkeys(keys))                    # (several convs share a key)
 
     def autotune(self, cache: Optional[dict] = None, reps: int = 3, save: Optional[str] = None, verbose: bool = False) -> dict:
         """time every (tile, split-K) candidate of every distinct conv shape on this GPU and keep the fastest."""
@@ -590,52 +568,28 @@ class Engine(NvaeBuilder, NdvaeBuilder, AvaeBuilder, ClassifierBuilder, E4EBuild
             key = conv_key(d)
             if key in cache:
                 continue
-            M = d.N * d.Ho * d.Wo
-            T = d.KH * d.KW * ((d.C1 + d.C2 + 31) // 32)
             best = None
-            modes = (1, 0) if d.w_hi else (0,)
-            halo = (5, 6, 7) if (d.w_hi and d.KH == 3 and d.KW == 3 and d.sn == 1 and d.sd == 1 and d.C2 == 0) else ()
-            if halo and self._want_frag(d):
-                halo = halo + (8,)
-            thin = (11,) if (d.w_hi and id(d) in self._thin_ok) else ()
-            pw = (12,) if (d.w_hi and id(d) in self._pw_ok and d.C2 == 0 and (d.N * d.Ho * d.Wo) % 128 == 0) else ()
-            for use_bf3, tile in [(m_, t_) for m_ in modes for t_ in (1, 2, 3, 4) + ((halo + thin + pw) if m_ else ())]:
-                bm, bn = {1: (128, 128), 2: (128, 64), 3: (64, 64), 4: (128, 32), 5: (128, 128), 6: (128, 64), 7: (128, 32), 8: (128, 128),
-                          11: (128, 32), 12: (128, 128)}[tile]
-                if bn >= 2 * max(32, d.Cout) and tile not in (4, 7):
+            for use_bf3, tile, splits in tile_candidates(d, lambda t: self._frag_weight(d, t) is not None):
+                t = L.ConvDesc.from_buffer_copy(d)
+                t.tile, t.splits = tile, splits
+                if TILES[tile].frag:
+                    t.w_frag = _ptr(TILES[tile].frag(self.store, self._conv_w[id(d)], d))
+                if not use_bf3:
+                    t.w_hi, t.w_lo = None, None
+                t.ws, t.ws_floats = (_ptr(self.ws), WS_FLOATS) if splits > 1 else (None, 0)
+                try:
+                    L.run(t, stream)
+                except L.GaError:                               # this kernel does not take the shape
                     continue
-                blocks = -(-M // bm) * -(-d.Cout // bn)
-                for splits in (1, 2, 4, 8, 16, 32):
-                    if splits > 1 and (blocks * splits > 2048 or T < 2 * splits or splits * M * d.Cout > WS_FLOATS):
-                        continue
-                    if tile >= 5 and splits > d.C1 // 32:          # the halo kernel splits K over 32-channel chunks
-                        continue
-                    if tile in (11, 12) and splits > 1:
-                        continue
-                    t = L.ConvDesc.from_buffer_copy(d)
-                    t.tile, t.splits = tile, splits
-                    if tile == 11:
-                        t.w_frag = _ptr(self.store.frag_thin(self._thin_ok[id(d)]))
-                    elif tile == 8:
-                        t.w_frag = _ptr(self.store.frag3(self._frag_ok[id(d)]))
-                    elif tile == 12:
-                        t.w_frag = _ptr(self.store.frag3(self._pw_ok[id(d)].reshape(d.Cout, d.C1), taps=1))
-                    if not use_bf3:
-                        t.w_hi, t.w_lo = None, None
-                    t.ws, t.ws_floats = (_ptr(self.ws), WS_FLOATS) if splits > 1 else (None, 0)
-                    try:
-                        L.run(t, stream)
-                    except L.GaError:                               # this kernel does not take the shape
-                        continue
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _ in range(reps):
-                        L.run(t, stream)
-                    e1.record()
-                    e1.synchronize()
-                    ms = e0.elapsed_time(e1) / reps
-                    if best is None or ms < best[0]:
-                        best = (ms, tile, splits, use_bf3)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(reps):
+                    L.run(t, stream)
+                e1.record()
+                e1.synchronize()
+                ms = e0.elapsed_time(e1) / reps
+                if best is None or ms < best[0]:
+                    best = (ms, tile, splits, use_bf3)
             cache[key] = (best[1], best[2], best[3])
             if verbose:
                 print(f'tune {key}: tile {best[1]} splits {best[2]} {best[0] * 1e3:.1f} us bf3 {best[3]}', flush=True)

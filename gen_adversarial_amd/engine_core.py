@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import json
 import os
-from typing import Dict, Optional
+from typing import Callable, Dict, NamedTuple, Optional
 
 import torch
 
@@ -143,7 +143,7 @@ def thin_ok(d, splits: Optional[int] = None) -> bool:
 
 def pw_ok(d, splits: Optional[int] = None) -> bool:
     """ga_conv2d runs d on tile 12 (conv_pw_frag_supports): the 1x1 kernel with its weight fragments read from d.w_frag (one tap;
-    without the copy the kernel gathers them from w_hi / w_lo, slower: the engine always builds it, _want_pw)"""
+    without the copy the kernel gathers them from w_hi / w_lo, slower: the engine always builds it, Engine._want)"""
     s = _splits(d, splits)
     if s != 1 or not _a16(d.w_frag) or not _bf3_vec_out(d, s):
         return False
@@ -156,6 +156,83 @@ def pw_ok(d, splits: Optional[int] = None) -> bool:
         return False
     mode = _pro_mode(d)
     return mode in (0x00, 0x01, 0x10, 0x11) or (mode == 0x20 and (d.Ho * d.Wo) % 16 == 0)
+
+
+class Tile(NamedTuple):
+    """what the host knows of one explicit tile code of ga_conv_desc.tile"""
+    code: int
+    bm: int                                 # output pixels x output channels of a workgroup
+    bn: int
+    ok: Callable                            # ok(d, splits): ga_conv2d takes d on this tile (the predicates above)
+    split_k: Optional[str] = 'step'         # split-K over 'step's of 32 channels of one tap, over 32-channel 'chunk's, or None
+    fallback: Optional[tuple] = None        # (tile with the same bits to demote to, whether it keeps the split-K factor)
+    frag: Optional[Callable] = None         # frag(store, w, d): the fragment-ordered weight copy d.w_frag points at
+    weight_ok: Optional[Callable] = None    # weight_ok(d, w): the tensor w has the layout (and the channel count) `frag` takes
+
+
+def _rows_of(d, w, taps: int) -> bool:
+    return w.dim() == 2 and w.shape[1] == taps * d.C1 and d.KH * d.KW == taps and d.C2 == 0
+
+
+TILES: Dict[int, Tile] = {t.code: t for t in (
+    Tile(1, 128, 128, lambda d, s: True), Tile(2, 128, 64, lambda d, s: True),
+    Tile(3, 64, 64, lambda d, s: True), Tile(4, 128, 32, lambda d, s: True),
+    Tile(5, 128, 128, lambda d, s: halo_ok(d, 5, s), 'chunk', (0, False)),
+    Tile(6, 128, 64, lambda d, s: halo_ok(d, 6, s), 'chunk', (0, False)),
+    Tile(7, 128, 32, lambda d, s: halo_ok(d, 7, s), 'chunk', (0, False)),
+    Tile(8, 128, 128, frag_ok, 'chunk', (5, True), lambda store, w, d: store.frag3(w),
+         lambda d, w: _rows_of(d, w, 9) and d.C1 % 32 == 0),
+    Tile(11, 128, 32, thin_ok, None, (7, False), lambda store, w, d: store.frag_thin(w),
+         lambda d, w: _rows_of(d, w, 9) and d.C1 in (32, 64)),
+    Tile(12, 128, 128, pw_ok, None, (0, False), lambda store, w, d: store.frag3(w.reshape(d.Cout, d.C1), taps=1),   # (the bits of tiles 1 - 4)
+         lambda d, w: w.numel() == d.Cout * d.C1 and d.C1 % 16 == 0),
+)}
+
+
+def resolve_tile(d, tile: int, splits: int, can_frag: Callable) -> tuple:
+    """the (tile, splits) d runs with when the tune table names (tile, splits) for its key.  conv_key does not encode pad / Wo / the
+    weight layout: a desc can share the key of an entry without being eligible for its tile.  It is then demoted along `fallback`
+    to a tile that gives the same bits (8 -> 5, 11 -> 7 when the halo kernel takes it), else to the library heuristic (0).
+    can_frag(tile) points d.w_frag at that tile's weight copy, or returns False."""
+    while tile in TILES:
+        t = TILES[tile]
+        if t.fallback is None or ((t.split_k or splits <= 1) and (t.frag is None or can_frag(tile)) and t.ok(d, splits)):
+            break
+        tile, splits = t.fallback[0], (splits if t.fallback[1] else 1)
+    return tile, splits
+
+
+def candidate_tiles(d, has_weight: Callable) -> tuple:
+    """the tile codes Engine.autotune times on the split-bf16 operands of d beside tiles 1 - 4; has_weight(tile): d's weight
+    tensor is known and `weight_ok` for that fragment-fed tile"""
+    if not d.w_hi:
+        return ()
+    halo = (5, 6, 7) if (d.KH == 3 and d.KW == 3 and d.sn == 1 and d.sd == 1 and d.C2 == 0) else ()
+    if halo and has_weight(8):
+        halo += (8,)
+    thin = (11,) if halo and has_weight(11) else ()
+    pw = (12,) if has_weight(12) and (d.sn, d.sd, d.pad) == (1, 1, 0) and (d.N * d.Ho * d.Wo) % 128 == 0 else ()
+    return halo + thin + pw
+
+
+def tile_candidates(d, has_weight: Callable) -> list:
+    """[(use_bf3, tile, splits), ...] in the order Engine.autotune times them (the first of two ties wins).  Not filtered by
+    `ok`: a candidate the library refuses is attempted and skipped"""
+    M = d.N * d.Ho * d.Wo
+    T = d.KH * d.KW * ((d.C1 + d.C2 + 31) // 32)
+    out = []
+    for use_bf3 in ((1, 0) if d.w_hi else (0,)):
+        for t in [TILES[c] for c in (1, 2, 3, 4) + (candidate_tiles(d, has_weight) if use_bf3 else ())]:
+            if t.bn >= 2 * max(32, d.Cout):
+                continue
+            blocks = -(-M // t.bm) * -(-d.Cout // t.bn)
+            for splits in (1, 2, 4, 8, 16, 32):
+                if splits > 1 and (t.split_k is None or blocks * splits > 2048 or T < 2 * splits or splits * M * d.Cout > WS_FLOATS):
+                    continue
+                if t.split_k == 'chunk' and splits > d.C1 // 32:        # the halo kernel splits K over 32-channel chunks
+                    continue
+                out.append((use_bf3, t.code, splits))
+    return out
 
 
 class WeightStore:
@@ -177,14 +254,12 @@ class WeightStore:
             self.bytes += 4 * w.numel()
         return self.splits[k][0], self.splits[k][1]
 
-    def frag3(self, w: torch.Tensor, m16: bool = False, taps: int = 9) -> torch.Tensor:
+    def frag3(self, w: torch.Tensor, taps: int = 9) -> torch.Tensor:
         """the split weights of a 3x3 conv ([Cout][9 * C] fp32, C % 32 == 0) in the MFMA-fragment order of ga_conv_desc.w_frag
         (bf16 [ceil(Cout/128)][C/32][taps][4 waves][2 k steps][hi | lo][64 lanes][8]); made once per tensor.
         taps=1: the same order for a 1x1 conv ([Cout][C], tile 12 — forward weights and the transposed copies of the ^T launches
-        alike); C % 16 == 0, a last half group is zero-padded to 32 channels.
-        m16: the order of the 16x16x32 fragments, [..][4 waves][2 halves of the wave's 32 channels][hi | lo][64 lanes][8], lane =
-        16 * (k octet of the 32-deep chunk) + channel"""
-        k = (('frag3m16' if m16 else 'frag3') + ('' if taps == 9 else f'_taps{taps}'), w.data_ptr())
+        alike); C % 16 == 0, a last half group is zero-padded to 32 channels."""
+        k = ('frag3' + ('' if taps == 9 else f'_taps{taps}'), w.data_ptr())
         if k not in self.splits:
             hi, lo = self.split(w)
             cout, kk = w.shape
@@ -196,8 +271,6 @@ class WeightStore:
             def arr(t):
                 tp = torch.zeros(nt * 128, taps * cp, dtype=torch.bfloat16, device=t.device)
                 tp[:cout, :kk] = t
-                if m16:     # [nt, wave, half, channel, tap, chunk, k octet, e] -> [nt, chunk, tap, wave, half, k octet, channel, e]
-                    return tp.view(nt, 4, 2, 16, taps, nkc, 4, 8).permute(0, 5, 4, 1, 2, 6, 3, 7)
                 # [nt, wave, row, tap, chunk, k step, lane half, e] -> [nt, chunk, tap, wave, k step, lane half, row, e]
                 return tp.view(nt, 4, 32, taps, nkc, 2, 2, 8).permute(0, 4, 3, 1, 5, 6, 2, 7)
             f = torch.stack([arr(hi), arr(lo)], dim=5).contiguous()          # hi | lo between the k step / half and the lane

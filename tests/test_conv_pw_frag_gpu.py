@@ -30,17 +30,24 @@ N, H, W = 16, 4, 4
 GUARD = 256
 
 
-def _run(cin, cout, tile, *, frag_copy=True, pro='none', dact=False, dact_rep=1, addend=False, addend2=False, addend_rep=1, w=None, seed=0):
+def _run(cin, cout, tile, *, frag_copy=True, pro='none', dact=False, dact_rep=1, addend=False, addend2=False, addend_rep=1, w=None, seed=0,
+         N=N, H=H, W=W, splits=1, c2=0):
     """-> (y [N, H, W, cout] with its guard region, the descriptor, the operand tensors for conv_ref); raises L.GaError"""
     g = torch.Generator(device=DEV).manual_seed(seed)
     rn = lambda *s, scale=1.0: torch.randn(*s, generator=g, device=DEV) * scale       # noqa: E731
     t = {'x': rn(N, H, W, cin)}
-    t['w'] = rn(cout, cin, scale=1 / math.sqrt(cin)) if w is None else w.contiguous()
+    t['w'] = rn(cout, cin + c2, scale=1 / math.sqrt(cin + c2)) if w is None else w.contiguous()
     t['bias'] = rn(cout, scale=0.5)
     d = L.ConvDesc()
     d.N, d.Hi, d.Wi, d.Ho, d.Wo, d.C1, d.Cout = N, H, W, H, W, cin, cout
     d.KH = d.KW = d.sn = d.sd = 1
-    d.ldx, d.ldy, d.tile, d.splits = cin, cout, tile, 1
+    d.ldx, d.ldy, d.tile, d.splits = cin, cout, tile, splits
+    if c2:
+        t['x2'] = rn(N, H, W, c2)
+        d.C2 = d.ldx2 = c2
+    if splits > 1:
+        t['ws'] = torch.empty(splits * N * H * W * cout, device=DEV)
+        d.ws_floats = t['ws'].numel()
     if pro == 'per_row':
         t['pro_scale'] = torch.rand(N, cin, generator=g, device=DEV) + 0.5
         t['pro_shift'] = rn(N, cin, scale=0.5)
@@ -63,13 +70,18 @@ def _run(cin, cout, tile, *, frag_copy=True, pro='none', dact=False, dact_rep=1,
     store = WeightStore(DEV)
     hi, lo = store.split(t['w'])
     # (a refused channel count has no fragment order: the request then carries the copy of the weights padded to the next k step)
-    frag = store.frag3(t['w'] if cin % 16 == 0 else torch.nn.functional.pad(t['w'], (0, -cin % 16)), taps=1)
+    frag = store.frag3(t['w'] if (cin + c2) % 16 == 0 else torch.nn.functional.pad(t['w'], (0, -(cin + c2) % 16)), taps=1)
     d.w_hi, d.w_lo = hi.data_ptr(), lo.data_ptr()
     if tile == 12 and frag_copy:
         d.w_frag = frag.data_ptr()
     y = torch.full((N * H * W * cout + GUARD,), float('nan'), device=DEV)
     d.y = y.data_ptr()
-    L.run(d, torch.cuda.current_stream().cuda_stream)
+    try:
+        L.run(d, torch.cuda.current_stream().cuda_stream)
+    except L.GaError as ex:             # a refused request launches nothing
+        torch.cuda.synchronize()
+        ex.desc, ex.untouched, ex.keep = d, bool(torch.isnan(y).all()), (t, hi, lo, frag)
+        raise
     torch.cuda.synchronize()
     return y, d, t, (hi, lo, frag)
 
@@ -130,3 +142,15 @@ def test_refuses_40_channels():
     """a channel count that is no multiple of the MFMA k step: GA_E_UNSUPPORTED, nothing launched"""
     with pytest.raises(L.GaError, match='UNSUPPORTED'):
         _run(40, 128, 12)
+
+
+@pytest.mark.parametrize('kw', [dict(N=15), dict(splits=2), dict(pro='per_row', N=128, H=3, W=3), dict(c2=64)],
+                         ids=['240_pixels', 'split_k', 'per_row_3x3_images', 'two_sources'])
+def test_refused_exactly_where_the_predicate_says_no(kw):
+    """the other direction of _check's `accepted => pw_ok`: descriptors one step outside tile 12's domain — pixels that are no
+    whole 128-pixel tiles, split-K, a per-row prologue on images of Ho * Wo % 16 != 0 pixels (1152 pixels: whole tiles), a second
+    source — are refused by the library, nothing written, and pw_ok says no"""
+    with pytest.raises(L.GaError, match='UNSUPPORTED') as ex:
+        _run(64, 128, 12, **kw)
+    assert ex.value.untouched, 'refused but wrote the output'
+    assert not pw_ok(ex.value.desc)

@@ -556,6 +556,78 @@ def test_apply_tuning_never_picks_a_tile_the_library_refuses(entry, ho, wo, pad)
         assert d.tile == {11: 7, 8: 5, 7: 7}[entry[0]], d.tile
 
 
+def _fake_conv_desc(n, h, w, c, cout, k, pad, c2=0):
+    """a split-bf16 k x k / stride-1 ConvDesc with fake (aligned) pointers, the output h x w"""
+    d = L.ConvDesc()
+    d.N, d.Hi, d.Wi, d.Ho, d.Wo, d.C1, d.C2, d.Cout = n, h + k - 1 - 2 * pad, w + k - 1 - 2 * pad, h, w, c, c2, cout
+    d.KH, d.KW, d.sn, d.sd, d.pad, d.ldx, d.ldx2, d.ldy = k, k, 1, 1, pad, c, c2, cout
+    d.x = d.w = d.y = d.w_hi = 4096
+    d.w_lo = 8192
+    d.x2 = 4096 if c2 else None
+    return d
+
+
+_RESOLVE_ENTRIES = [(5, 1), (5, 2), (7, 1), (8, 1), (8, 2), (11, 1), (11, 2), (12, 1), (12, 2)]
+_Z = (0, 1)
+_RESOLVE_3X3 = {            # (Ho, Wo, pad) of a 2-row 3x3 conv, 32 -> 64 channels: (tile, splits) per entry of _RESOLVE_ENTRIES
+    (16, 48, 1): [_Z, _Z, _Z, _Z, _Z, (11, 1), _Z, _Z, _Z],
+    (16, 32, 0): [_Z, _Z, _Z, _Z, _Z, _Z, _Z, _Z, _Z],
+    (12, 16, 1): [_Z, _Z, _Z, _Z, _Z, _Z, _Z, _Z, _Z],
+    (8, 32, 1): [(5, 1), _Z, (7, 1), (8, 1), _Z, (11, 1), (7, 1), _Z, _Z],
+    (4, 256, 1): [(5, 1), _Z, (7, 1), (5, 1), _Z, (7, 1), (7, 1), _Z, _Z],
+}
+_RESOLVE_1X1 = {            # (images of 4 x 4, input channels) of a 1x1 conv to 128 channels
+    (16, 64): [_Z, _Z, _Z, _Z, _Z, _Z, _Z, (12, 1), _Z],
+    (15, 64): [_Z, _Z, _Z, _Z, _Z, _Z, _Z, _Z, _Z],            # 240 pixels: not whole 128-pixel tiles
+    (16, 40): [_Z, _Z, _Z, _Z, _Z, _Z, _Z, _Z, _Z],            # a channel count tile 12 refuses
+}
+
+
+def test_resolve_tile_demotes_like_the_hand_written_chain():
+    """engine_core.resolve_tile on every tune-table entry kind x eight geometries, the fragment copy always at hand (can_frag
+    sets a fake aligned w_frag): tile 12 and the "fragment copy present" branches, which a dry-run engine never reaches.
+    The expected (tile, splits) are what Engine.apply_tuning of commit cef3822 — the hand-written chain 8 -> 5, 11 -> 7,
+    5 / 6 / 7 -> 0, 12 -> 0 — gave for these descriptors, run on the CPU with its three _want_* methods replaced by one that sets a
+    fake w_frag and answers True for the descriptors Engine.conv had registered for that tile."""
+    from gen_adversarial_amd.engine_core import resolve_tile
+
+    def got(d):
+        out = []
+        for tile, splits in _RESOLVE_ENTRIES:
+            d.w_frag = None
+            out.append(resolve_tile(d, tile, splits, lambda t: setattr(d, 'w_frag', 4096) is None))
+        return out
+    for (ho, wo, pad), want in _RESOLVE_3X3.items():
+        assert got(_fake_conv_desc(2, ho, wo, 32, 64, 3, pad)) == want, (ho, wo, pad)
+    for (n, c), want in _RESOLVE_1X1.items():
+        assert got(_fake_conv_desc(n, 4, 4, c, 128, 1, 0)) == want, (n, c)
+
+
+def _cands(use_bf3, tiles_splits):
+    return [(use_bf3, t, s) for t, ss in tiles_splits for s in ss]
+
+
+def test_tile_candidates_are_the_ones_autotune_enumerated():
+    """engine_core.tile_candidates: the (use_bf3, tile, splits) candidates and their order (the first of two ties wins) are
+    those of the inline enumeration of Engine.autotune at commit cef3822, taken from an instrumented copy of that loop"""
+    from gen_adversarial_amd.engine_core import TILES, tile_candidates
+
+    def got(d, w):
+        return tile_candidates(d, lambda t: TILES[t].weight_ok(d, w))
+    s16, s4, s1 = (1, 2, 4, 8, 16), (1, 2, 4), (1,)
+    d = _fake_conv_desc(2, 16, 16, 128, 128, 3, 1)
+    assert got(d, torch.zeros(128, 9 * 128)) == (
+        _cands(1, [(1, s16), (2, s16), (3, s16), (4, s16), (5, s4), (6, s4), (7, s4), (8, s4)])
+        + _cands(0, [(1, s16), (2, s16), (3, s16), (4, s16)]))
+    d = _fake_conv_desc(2, 64, 64, 32, 64, 3, 1)            # 64 output channels: no 128-wide tile; one 32-channel chunk: no split-K
+    assert got(d, torch.zeros(64, 9 * 32)) == (
+        _cands(1, [(2, s4), (3, s4), (4, s4), (6, s1), (7, s1), (11, s1)]) + _cands(0, [(2, s4), (3, s4), (4, s4)]))
+    d = _fake_conv_desc(16, 4, 4, 64, 128, 1, 0)
+    assert got(d, torch.zeros(128, 64)) == _cands(1, [(1, s1), (2, s1), (3, s1), (4, s1), (12, s1)]) + _cands(0, [(1, s1), (2, s1), (3, s1), (4, s1)])
+    d = _fake_conv_desc(16, 4, 4, 64, 128, 1, 0, c2=32)     # a second source: no fragment-fed tile
+    assert got(d, torch.zeros(128, 96)) == _cands(1, [(1, s1), (2, s1), (3, s1), (4, s1)]) + _cands(0, [(1, s1), (2, s1), (3, s1), (4, s1)])
+
+
 def test_tile_predicates_follow_the_header():
     """engine_core.halo_ok / frag_ok / thin_ok at the edges ga_conv_desc.tile documents"""
     from types import SimpleNamespace

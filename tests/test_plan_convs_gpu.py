@@ -3,7 +3,8 @@ Every dense contraction of the three shipped plans, as tuned, against the float6
 
 The engines are the ones bench.py times, built by the same code (configs[1] NVAE + VGG at bench.py's 1024-row chunk, the
 configs[2] e4e defender at 32 rows and the configs[4] Style-Transformer defender at 64 rows, EoT 32): apply_tuning makes its
-real choices only on a GPU (tile 8 / tile 11 need their weight fragments).  Each distinct ConvDesc of their forward and
+real choices only on a GPU (tiles 8, 11 and 12 need their weight fragments; a rebuilt descriptor gets the copy its tile reads from
+engine_core.TILES, as the engine does).  Each distinct ConvDesc of their forward and
 backward plans runs on buffers of this test with fewer rows, fresh weights and NaN-filled outputs, and must
   - be accepted (GA_E_UNSUPPORTED on a shipped descriptor is a plan the engine would fail to run),
   - meet |y - ref| <= tau * scale + slack + 2^-22 |ref| on every element (tau_bf3 / tau_fp32 of tests/convref.py),
@@ -33,7 +34,7 @@ if not torch.cuda.is_available():
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import convref as R                                                      # noqa: E402
 from gen_adversarial_amd import _lib as L                                # noqa: E402
-from gen_adversarial_amd.engine_core import WeightStore, frag_ok, halo_ok, thin_ok, _bf3_vec_out  # noqa: E402
+from gen_adversarial_amd.engine_core import TILES as TILE_TABLE, WeightStore, frag_ok, halo_ok, thin_ok, _bf3_vec_out  # noqa: E402
 
 DEV = 'cuda:0'
 ALL = os.environ.get('GA_TEST_ALL_PLAN_CONVS', '0') == '1'
@@ -41,7 +42,11 @@ GUARD = 256                                 # floats past the last output pixel 
 OPERANDS = ('x', 'x2', 'w', 'bias', 'pro_scale', 'pro_shift', 'addend', 'addend2', 'dact_x', 'dact_scale', 'dact_shift', 'y',
             'w_hi', 'w_lo', 'w_frag', 'ws')
 INTS = tuple(f for f, _ in L.ConvDesc._fields_ if f not in OPERANDS + ('ws_floats', 'x_bytes', 'x2_bytes', 'w_bytes'))
-TILES = (0, 1, 2, 3, 4, 5, 6, 7, 8, 11)
+TILES = (0, 1, 2, 3, 4, 5, 6, 7, 8, 11, 12)
+
+
+def _frag_fed(tile):
+    return tile in TILE_TABLE and TILE_TABLE[tile].frag is not None
 
 
 class Conv:
@@ -51,7 +56,7 @@ class Conv:
     def __init__(self, d, where=''):
         self.f = {k: int(getattr(d, k)) for k in INTS}
         self.has = frozenset(k for k in OPERANDS if getattr(d, k) and k not in ('ws', 'w_frag'))
-        self.frag = bool(d.w_frag) and d.tile in (8, 11)
+        self.frag = bool(d.w_frag) and _frag_fed(d.tile)
         self.align = tuple(sorted((k, getattr(d, k) % 16 // 4) for k in self.has))
         self.alias = tuple(k for k in ('addend', 'addend2') if getattr(d, k) and getattr(d, k) == d.y)
         self.where = [where]
@@ -232,8 +237,8 @@ def run_conv(c, n=None, seed=0, zero_lo=False, w=None):
         hi, lo = store.split(wt)
         d.w_hi, d.w_lo = hi.data_ptr(), lo.data_ptr()
         t['_keep'] = [wt, hi, lo]
-        if c.frag:
-            fr = store.frag_thin(wt) if c.tile == 11 else store.frag3(wt)
+        if c.frag and _frag_fed(c.tile):
+            fr = TILE_TABLE[c.tile].frag(store, wt, d)
             d.w_frag = fr.data_ptr()
             t['_keep'].append(fr)
     stream = torch.cuda.current_stream().cuda_stream
@@ -296,12 +301,14 @@ def test_plan_conv_descriptors(plan_convs):
 
 
 def _synthetic(tile):
-    """a 3x3, 32 -> 64 conv on 8 x 16 images that every tile takes"""
+    """a 3x3, 32 -> 64 conv on 8 x 16 images that every 3x3 tile takes; tile 12: a 1x1, 64 -> 128 conv on 16 images of 4 x 4"""
     d = L.ConvDesc()
     d.N, d.Hi, d.Wi, d.C1, d.Ho, d.Wo, d.Cout, d.KH, d.KW, d.sn, d.sd, d.pad = 8, 8, 16, 32, 8, 16, 64, 3, 3, 1, 1, 1
-    d.ldx, d.ldy, d.tile, d.splits = 32, 64, tile, 1
+    if tile == 12:
+        d.N, d.Hi, d.Wi, d.C1, d.Ho, d.Wo, d.Cout, d.KH, d.KW, d.pad = 16, 4, 4, 64, 4, 4, 128, 1, 1, 0
+    d.ldx, d.ldy, d.tile, d.splits = d.C1, d.Cout, tile, 1
     d.x = d.w = d.y = d.w_hi = d.w_lo = 4096
-    d.w_frag = 4096 if tile in (8, 11) else None
+    d.w_frag = 4096 if _frag_fed(tile) else None
     return Conv(d, f'synthetic tile {tile}')
 
 

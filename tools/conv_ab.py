@@ -30,7 +30,6 @@ b = torch.randn(Cout, device=dev, generator=g) * 0.1
 store = WeightStore(dev)
 hi, lo = store.split(w)
 frag = store.frag3(w, taps=KK)
-frag16 = store.frag3(w, m16=True) if K == 3 else None
 frag_thin = store.frag_thin(w) if Cin in (32, 64) and K == 3 else None
 pro = os.environ.get('GA_AB_PRO') == 'row'
 ps, pt = torch.rand(N, Cin, device=dev, generator=g) + 0.5, torch.randn(N, Cin, device=dev, generator=g) * 0.5
@@ -44,7 +43,7 @@ for t in tiles:
     d.N, d.Hi, d.Wi, d.Ho, d.Wo, d.KH, d.KW, d.sn, d.sd, d.pad, d.tile, d.pro_act = N, H, H, H, H, K, K, 1, 1, K // 2, t, act
     if pro:
         d.pro_scale, d.pro_shift, d.pro_per_row = ps.data_ptr(), pt.data_ptr(), 1
-    d.w_hi, d.w_lo, d.w_frag = hi.data_ptr(), lo.data_ptr(), (frag16 if t in (9, 10) else frag_thin if t == 11 else frag).data_ptr()
+    d.w_hi, d.w_lo, d.w_frag = hi.data_ptr(), lo.data_ptr(), (frag_thin if t == 11 else frag).data_ptr()
     if os.environ.get('GA_AB_BWD'):     # the epilogue of a backward conv: act' of a saved activation and an identity-skip addend
         d.dact_x, d.lddact, d.dact_act, d.addend, d.ldadd = dact.data_ptr(), Cout, 1, add.data_ptr(), Cout
     L.run(d)
