@@ -97,12 +97,11 @@ __device__ __forceinline__ void acc_walk(floatx4 (&acc)[TM2][TN2], const int lan
 // Tile rows -> output pixels: row r of the tile is pixel m0 + r (tiles that are runs of the [N, Ho, Wo] pixel index: the default,
 // tw_shift = 31) or, for 2-D tiles of 2^tw_shift columns (conv_thin3: 8 x 16 pixel tiles of a wide image), pixel
 // m0 + (r >> tw_shift) * row_stride + (r & (2^tw_shift - 1)) with m0 the tile's top-left pixel and row_stride = Wo.
-template <int WM, int WN, int TM, int TN, class ACC>
-__device__ __forceinline__ void conv_epilogue(const ga_conv_desc& d, ACC& acc, float* smem, const int m0,
-                                              const int n0, const int M, const int vec_out, const int splits, const int split,
-                                              const int tw_shift = 31, const int row_stride = 0) {
-    const int tw_mask = (int)((1u << tw_shift) - 1u);
-    auto mrow = [&](const int r) __attribute__((always_inline)) { return m0 + (r >> tw_shift) * row_stride + (r & tw_mask); };
+// conv_epilogue_rows takes the map itself: mrow(r) = output pixel of tile row r, any function of the workgroup's own indices
+// (conv_quad3: row = 32 * position in the quadrant + image).
+template <int WM, int WN, int TM, int TN, class ACC, class MROW>
+__device__ __forceinline__ void conv_epilogue_rows(const ga_conv_desc& d, ACC& acc, float* smem, const MROW& mrow,
+                                                   const int n0, const int M, const int vec_out, const int splits, const int split) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
     constexpr int LDC = BN + 4;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -218,6 +217,15 @@ __device__ __forceinline__ void conv_epilogue(const ga_conv_desc& d, ACC& acc, f
             }
         });
     }
+}
+
+template <int WM, int WN, int TM, int TN, class ACC>
+__device__ __forceinline__ void conv_epilogue(const ga_conv_desc& d, ACC& acc, float* smem, const int m0,
+                                              const int n0, const int M, const int vec_out, const int splits, const int split,
+                                              const int tw_shift = 31, const int row_stride = 0) {
+    const int tw_mask = (int)((1u << tw_shift) - 1u);
+    auto mrow = [&](const int r) __attribute__((always_inline)) { return m0 + (r >> tw_shift) * row_stride + (r & tw_mask); };
+    conv_epilogue_rows<WM, WN, TM, TN>(d, acc, smem, mrow, n0, M, vec_out, splits, split);
 }
 
 }  // namespace ga

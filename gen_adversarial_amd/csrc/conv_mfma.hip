@@ -421,6 +421,8 @@ int conv_bf3_dispatch(const ga_conv_desc& d, hipStream_t stream, int tile, int v
 int conv_bf3_supports(const ga_conv_desc& d);
 int conv_halo3_dispatch(const ga_conv_desc& d, hipStream_t stream, int tile, int vec_out, int splits);  // conv_halo3.hip
 int conv_halo3_supports(const ga_conv_desc& d);
+int conv_quad3_dispatch(const ga_conv_desc& d, hipStream_t stream, int vec_out, int splits);             // conv_quad3.hip
+int conv_quad3_supports(const ga_conv_desc& d, int splits);
 int conv_thin3_dispatch(const ga_conv_desc& d, hipStream_t stream, int vec_out, int splits);             // conv_thin3.hip
 int conv_thin3_supports(const ga_conv_desc& d);
 int conv_pw_frag_dispatch(const ga_conv_desc& d, hipStream_t stream, int vec_out);                       // conv_pw_frag.hip
@@ -550,6 +552,9 @@ extern "C" int ga_conv2d(const ga_conv_desc* dp, void* stream_) {
     } else if (tile == 12) {            // 1x1 with the weight fragments read from global memory (explicit request only; w_frag with one tap)
         if (!(bf3 && vec_out && conv_pw_frag_supports(d, splits))) return GA_E_UNSUPPORTED;
         rc = conv_pw_frag_dispatch(k, stream, vec_out);
+    } else if (tile == 9) {             // quadrant tile: 3x3 on 4 x 4 images without the products of the zero frame (explicit request only; w_frag in the tile-8 order)
+        if (!(bf3 && vec_out && conv_quad3_supports(d, splits))) return GA_E_UNSUPPORTED;
+        rc = conv_quad3_dispatch(k, stream, vec_out, splits);
     } else if (tile >= 5 && tile <= 8) { // halo-staged 3x3 (explicit request only: the tune table names it per shape)
         if (!(bf3 && vec_out && conv_halo3_supports(d))) return GA_E_UNSUPPORTED;
         rc = conv_halo3_dispatch(k, stream, tile, vec_out, splits);

@@ -39,7 +39,7 @@ def _ptr(t: Optional[torch.Tensor]):
 
 # ---- which explicit tile codes ga_conv2d takes for a descriptor (GA_E_UNSUPPORTED otherwise).  A restatement of the checks in
 #      csrc/conv_mfma.hip (ga_conv2d: the split-bf16 and vector-output preconditions), csrc/conv_bf3.hip (conv_bf3_supports),
-#      csrc/conv_halo3.hip (conv_halo3_supports, halo_geometry, launch_halo, launch_halo_bd), csrc/conv_thin3.hip
+#      csrc/conv_halo3.hip (conv_halo3_supports, halo_geometry, launch_halo, launch_halo_bd), csrc/conv_quad3.hip (conv_quad3_supports), csrc/conv_thin3.hip
 #      (conv_thin3_supports) and csrc/conv_pw_frag.hip (conv_pw_frag_supports); tests/test_plan_convs_gpu.py checks that the library refuses exactly what these reject.
 _HALO_HK, _HALO_LDH = 32, 40                # conv_halo3.hip: channels per chunk, bf16 per LDS pixel row
 _BF3_MODES = (0x000, 0x100, 0x001, 0x002, 0x003, 0x004, 0x010, 0x011, 0x020, 0x021)
@@ -131,6 +131,15 @@ def frag_ok(d, splits: Optional[int] = None) -> bool:
     return tab_off * 4 + tab <= 80 * 1024
 
 
+def quad_ok(d, splits: Optional[int] = None) -> bool:
+    """ga_conv2d runs d on tile 9 (conv_quad3_supports): what the halo kernels take, on 4 x 4 images in whole groups of 32, with tile
+    8's d.w_frag (a batch of fewer than 32 images runs as one partial group).  (Tile 8's LDS bound does not apply: the kernel keeps two 36-KB patch buffers and no tables at any channel count.)"""
+    s = _splits(d, splits)
+    if not d.w_frag or not _a16(d.w_frag) or not _bf3_vec_out(d, s) or not _halo_3x3(d):
+        return False
+    return d.Hi == 4 and d.Wi == 4 and (d.N % 32 == 0 or d.N < 32) and s <= d.C1 // _HALO_HK
+
+
 def thin_ok(d, splits: Optional[int] = None) -> bool:
     """ga_conv2d runs d on tile 11: the persistent weights-resident 3x3 kernel of 32 or 64 input channels (d.w_frag in its order)"""
     s = _splits(d, splits)
@@ -182,6 +191,8 @@ TILES: Dict[int, Tile] = {t.code: t for t in (
     Tile(7, 128, 32, lambda d, s: halo_ok(d, 7, s), 'chunk', (0, False)),
     Tile(8, 128, 128, frag_ok, 'chunk', (5, True), lambda store, w, d: store.frag3(w),
          lambda d, w: _rows_of(d, w, 9) and d.C1 % 32 == 0),
+    Tile(9, 128, 128, quad_ok, 'chunk', (8, True), lambda store, w, d: store.frag3(w),
+         lambda d, w: _rows_of(d, w, 9) and d.C1 % 32 == 0),
     Tile(11, 128, 32, thin_ok, None, (7, False), lambda store, w, d: store.frag_thin(w),
          lambda d, w: _rows_of(d, w, 9) and d.C1 in (32, 64)),
     Tile(12, 128, 128, pw_ok, None, (0, False), lambda store, w, d: store.frag3(w.reshape(d.Cout, d.C1), taps=1),   # (the bits of tiles 1 - 4)
@@ -192,7 +203,7 @@ TILES: Dict[int, Tile] = {t.code: t for t in (
 def resolve_tile(d, tile: int, splits: int, can_frag: Callable) -> tuple:
     """the (tile, splits) d runs with when the tune table names (tile, splits) for its key.  conv_key does not encode pad / Wo / the
     weight layout: a desc can share the key of an entry without being eligible for its tile.  It is then demoted along `fallback`
-    to a tile that gives the same bits (8 -> 5, 11 -> 7 when the halo kernel takes it), else to the library heuristic (0).
+    to a tile that gives the same values (9 -> 8 -> 5, 11 -> 7 when the halo kernel takes it), else to the library heuristic (0).
     can_frag(tile) points d.w_frag at that tile's weight copy, or returns False."""
     while tile in TILES:
         t = TILES[tile]
@@ -210,6 +221,8 @@ def candidate_tiles(d, has_weight: Callable) -> tuple:
     halo = (5, 6, 7) if (d.KH == 3 and d.KW == 3 and d.sn == 1 and d.sd == 1 and d.C2 == 0) else ()
     if halo and has_weight(8):
         halo += (8,)
+        if d.Hi == 4 and d.Wi == 4 and (d.N % 32 == 0 or d.N < 32) and has_weight(9):     # the quadrant tile: 4 x 4 images only
+            halo += (9,)
     thin = (11,) if halo and has_weight(11) else ()
     pw = (12,) if has_weight(12) and (d.sn, d.sd, d.pad) == (1, 1, 0) and (d.N * d.Ho * d.Wo) % 128 == 0 else ()
     return halo + thin + pw

@@ -86,6 +86,8 @@ typedef struct ga_conv_desc {
                                               pad 1, C1 % 32 == 0, 128 % Wo == 0 or Wo % 128 == 0, w_hi/w_lo given;
                                               GA_E_UNSUPPORTED otherwise); 8 = 128x128 on the same kernel with the weight
                                               fragments read from global memory (w_frag given, 128 % Wo == 0);
+                                              9 = the quadrant tile: tile 8's structure for Hi == Wi == 4 and N % 32 == 0 or N < 32 (same w_frag), a
+                                              workgroup = one 2 x 2 quadrant of 32 images, the products with the zero padding left out;
                                               11 = persistent weights-resident 3x3 for C1 == 32 or 64 on 8 x 16 pixel tiles (3x3, stride 1,
                                               pad 1, Ho % 8 == 0, Wo % 16 == 0, no split-K, w_frag given in the tile-11 order below);
                                               12 = 128x128 for 1x1 / stride 1 / pad 0 with the weight fragments read from global memory (one
@@ -104,7 +106,7 @@ typedef struct ga_conv_desc {
     int addend_rep;                        /* > 1: addend has N/addend_rep rows, row n reads addend row n / addend_rep
                                               (EoT replicas sharing one encoder feature map) */
     int flags;                             /* GA_CONV_* bits below */
-    const void* w_frag;                    /* optional, tile 8 only: the split weights of a 3x3 conv in MFMA-fragment order, bf16
+    const void* w_frag;                    /* optional, tiles 8 and 9: the split weights of a 3x3 conv in MFMA-fragment order, bf16
                                               [ceil(Cout/128)][C1/32][9 taps][4 waves][2 k steps][hi | lo][64 lanes][8]: element e of
                                               lane l = W[128 t + 32 wave + (l & 31)][tap * C1 + 32 chunk + 16 kstep + 8 (l >> 5) + e]
                                               (rows >= Cout zero).  The halo kernel then reads its B fragments from global memory:
