@@ -38,9 +38,9 @@ class _PreprocessDefense(torch.nn.Module, _EngineOwner):
         self.image_size = batch.shape[-1]
         return super().class_jacobian_rows(batch, rep, classes)
 
-    def forward_rows(self, batch: torch.Tensor, rep: int = 1) -> torch.Tensor:
+    def forward_rows(self, batch: torch.Tensor, rep: int = 1, first_row: int = 0) -> torch.Tensor:
         self.image_size = batch.shape[-1]
-        return self._run(batch, rep, False)[0]
+        return self._run(batch, rep, False, first_row=first_row)[0]
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return self.forward_rows(x, 1)

@@ -71,8 +71,8 @@ class AVaeDefenseModel(torch.nn.Module, _EngineOwner):
         eng = Engine.bare(rows, device=self.device, store=self._store, rep=rep, resolution=(3, D, D), alphas=[], cot_rep=cot_rep)
         return eng.build_avae_defense(av.state_dict, av.spec, self.kernel_size, clf.state_dict, clf.spec)
 
-    def forward_rows(self, batch: torch.Tensor, rep: int = 1, preds_only: bool = True):
-        logits, purified = self._run(batch, rep, not preds_only)
+    def forward_rows(self, batch: torch.Tensor, rep: int = 1, preds_only: bool = True, first_row: int = 0):
+        logits, purified = self._run(batch, rep, not preds_only, first_row=first_row)
         return logits if preds_only else (logits, purified)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:

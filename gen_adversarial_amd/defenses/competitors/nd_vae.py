@@ -81,8 +81,8 @@ class NDVaeDefenseModel(torch.nn.Module, _EngineOwner):
                           noise_eps=self.noise_std if with_noise else 0.0, cot_rep=cot_rep)
         return eng.build_ndvae_defense(nd.state_dict, nd.spec, nd.h, clf.state_dict, clf.spec)
 
-    def forward_rows(self, batch: torch.Tensor, rep: int = 1, preds_only: bool = True):
-        logits, purified = self._run(batch, rep, not preds_only)
+    def forward_rows(self, batch: torch.Tensor, rep: int = 1, preds_only: bool = True, first_row: int = 0):
+        logits, purified = self._run(batch, rep, not preds_only, first_row=first_row)
         return logits if preds_only else (logits, purified)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:

@@ -21,6 +21,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
+from ... import _lib as L
 from ...engine import Engine, WeightStore
 
 
@@ -28,9 +29,9 @@ class _EngineFn(torch.autograd.Function):
     """One forward of an Engine; backward replays the engine's backward plan (dX only)."""
 
     @staticmethod
-    def forward(ctx, x: torch.Tensor, owner, eng: Engine, want_purified: bool):
+    def forward(ctx, x: torch.Tensor, owner, eng: Engine, want_purified: bool, first_row: int = 0):
         eng.x_in.copy_(x.detach())
-        owner._fill_noise(eng)
+        owner._fill_noise(eng, first_row)
         eng.forward()
         eng.version += 1
         ctx.eng, ctx.owner, ctx.version = eng, owner, eng.version
@@ -62,14 +63,14 @@ class _EngineFn(torch.autograd.Function):
         if use_purified:
             eng.dpurified.copy_(dpurified)
         if not use_logits and not use_purified:
-            return torch.zeros_like(ctx.x), None, None, None
+            return torch.zeros_like(ctx.x), None, None, None, None
         if getattr(ctx.owner, 'bpda', False):               # BPDA: identity in place of the purifier's Jacobian
             if not use_logits:
-                return torch.zeros_like(ctx.x), None, None, None
+                return torch.zeros_like(ctx.x), None, None, None, None
             eng.backward(identity_purifier=True)
         else:
             eng.backward(from_logits=use_logits, from_purified=use_purified)
-        return eng.dx.clone(), None, None, None
+        return eng.dx.clone(), None, None, None, None
 
 
 class _EngineJacobian:
@@ -171,7 +172,68 @@ class _EngineOwner:
         more rows than a call needs (attacks that drop finished images call with fewer rows): row r of a call uses draw r."""
         self._fixed_noise = None if eps is None and input_noise is None else (eps, input_noise)
 
-    def _fill_noise(self, eng: Engine):
+    # seeded draws: None = torch's generator (the default); else (seed, draw of the next call, absolute row of a call's first row)
+    _noise_seed: Optional[int] = None
+    _noise_draw = 0
+    _noise_row0 = 0
+
+    def seeded_noise(self, seed: Optional[int], draw: int = 0, first_row: int = 0):
+        """Draw the noise of the next calls on the device with ga_randn (include/ga_ops.h) instead of torch's generator; None
+        restores torch's draws.  Element e of row r of a call is then a pure function of (seed, draw, tensor, first_row + r, e) —
+        latent group i is tensor i, the input noise GA_RANDN_STREAM_INPUT — that gen_adversarial_amd.noise.reference_randn restates
+        on the CPU; it does not depend on how rows are cut into calls.  Every call that draws advances `draw` by one; `first_row`
+        (images before this call x EoT, for shards and chunked callers) stays until set again, and a call's own `first_row`
+        argument (forward_rows) is added to it.  `first_row` may also be a sequence with one entry per image of the next calls
+        (images that are not neighbours in the dataset, e.g. an r::W shard's batch): the EoT rows of image k of a call then start at
+        first_row[k]; a call with fewer images uses the leading entries (an attack that drops finished images loses the others'
+        identity).  Only forward_rows takes a per-call offset: class_jacobian_rows, forward_candidates and loss_and_alpha_grad draw
+        at the owner's first_row, so a chunked caller of those calls seeded_noise again per chunk.
+        fixed_noise(...) wins while it is set, and does not advance the counter."""
+        if seed is not None and not 0 <= int(seed) < 1 << 64:
+            raise ValueError('seed: 0 <= seed < 2^64 expected')
+        rows = [int(r) for r in first_row] if hasattr(first_row, '__len__') else int(first_row)
+        if not 0 <= int(draw) < 1 << 32 or min(rows if isinstance(rows, list) else [rows], default=0) < 0:
+            raise ValueError('draw: 0 <= draw < 2^32 and first_row >= 0 expected')
+        self._noise_seed = None if seed is None else int(seed)
+        self._noise_draw, self._noise_row0 = int(draw), rows
+
+    def _randn(self, eng: Engine, t: torch.Tensor, tensor: int, row0: int, scale: float = 1.0, coef: Optional[torch.Tensor] = None):
+        if not t.is_contiguous() or t.dtype != torch.float32:
+            raise RuntimeError('ga_randn fills contiguous fp32 tensors')
+        if isinstance(row0, list):                                  # one launch per image: its `rep` rows start at the image's own row
+            n, rep = t.shape[0] // eng.rep, eng.rep
+            if n > len(row0):
+                raise ValueError(f'seeded_noise was given the first rows of {len(row0)} images, the call has {n}')
+            for k in range(n):
+                self._randn(eng, t[k * rep:(k + 1) * rep], tensor, row0[k], scale, None if coef is None else coef[k * rep:(k + 1) * rep])
+            return
+        rows, inner = t.shape[0], t[0].numel()
+        tail = (None, 0.0, None, 0)                                 # coef, coef_eps, ws, ws_floats
+        if coef is not None:
+            need = rows * ((inner // 4 + 255) // 256)               # one partial sum per workgroup of 256 quads
+            ws = getattr(eng, '_randn_ws', None)
+            if ws is None or ws.numel() < need:
+                ws = eng._randn_ws = torch.empty(need, device=t.device, dtype=torch.float32)
+            tail = (coef.data_ptr(), eng.noise_eps, ws.data_ptr(), ws.numel())
+        L.check(L.lib.ga_randn(t.data_ptr(), rows, inner, self._noise_seed, self._noise_draw, tensor, row0, scale, 0, *tail, eng.stream()),
+                'ga_randn')
+
+    def _fill_noise_seeded(self, eng: Engine, first_row: int):
+        row0 = self._noise_row0
+        row0 = [r + int(first_row) for r in row0] if isinstance(row0, list) else row0 + int(first_row)
+        for i, e in enumerate(eng.eps):
+            self._randn(eng, e, i, row0, float(getattr(eng, 'eps_std', 1.0)))
+        if eng.noise is not None:
+            if getattr(eng, 'noise_is_std', False):
+                self._randn(eng, eng.noise, L.GA_RANDN_STREAM_INPUT, row0)
+                eng.noise_coef.fill_(eng.noise_eps)
+            else:
+                self._randn(eng, eng.noise, L.GA_RANDN_STREAM_INPUT, row0, coef=eng.noise_coef)
+        self._noise_draw = (self._noise_draw + 1) & 0xFFFFFFFF
+
+    def _fill_noise(self, eng: Engine, first_row: int = 0):
+        if self._fixed_noise is None and self._noise_seed is not None:
+            return self._fill_noise_seeded(eng, first_row)
         eps, inp = self._fixed_noise if self._fixed_noise is not None else (None, None)
         for i, e in enumerate(eng.eps):                      # one draw per latent group, even when alpha == 0
             if eps is not None:
@@ -232,7 +294,7 @@ class _EngineOwner:
             raise ValueError(f'expected {eng.resolution[1]}x{eng.resolution[2]} images, got {tuple(batch.shape[2:])}')
         return _EngineJacobian(self, eng, batch, rep, classes)
 
-    def _run(self, batch: torch.Tensor, rep: int, want_purified: bool, with_noise: bool = True):
+    def _run(self, batch: torch.Tensor, rep: int, want_purified: bool, with_noise: bool = True, first_row: int = 0):
         if batch.dim() != 4 or batch.shape[1] != 3:
             raise ValueError('expected a (B, 3, H, W) image batch')
         differentiable = torch.is_grad_enabled() and batch.requires_grad
@@ -240,7 +302,7 @@ class _EngineOwner:
         eng = self._engine(batch.shape[0] * rep, rep, with_noise, forward_only=not differentiable)
         if tuple(batch.shape[2:]) != tuple(eng.resolution[1:]):
             raise ValueError(f'expected {eng.resolution[1]}x{eng.resolution[2]} images, got {tuple(batch.shape[2:])}')
-        return _EngineFn.apply(batch, self, eng, want_purified)
+        return _EngineFn.apply(batch, self, eng, want_purified, first_row)
 
 
 class BaseClassificationModel(ABC, _EngineOwner):
@@ -286,8 +348,8 @@ class BaseClassificationModel(ABC, _EngineOwner):
         self.image_size = batch.shape[-1]
         return self.class_jacobian_rows(batch, 1, classes)
 
-    def forward_rows(self, batch: torch.Tensor, rep: int = 1) -> torch.Tensor:
-        return self._run(batch, rep, False)[0]
+    def forward_rows(self, batch: torch.Tensor, rep: int = 1, first_row: int = 0) -> torch.Tensor:
+        return self._run(batch, rep, False, first_row=first_row)[0]
 
     def __call__(self, batch: torch.Tensor) -> torch.Tensor:
         """(B,3,H,W) in [0,1] -> un-normalised predictions (B, n_classes)."""
@@ -326,8 +388,8 @@ class MLVGMDefenseModel(ABC, _EngineOwner):
     def _current_alphas(self):
         return [float(a) for a in self.interpolation_alphas]      # alpha learning overwrites the list in place
 
-    def forward_rows(self, batch: torch.Tensor, rep: int = 1, preds_only: bool = True):
-        logits, purified = self._run(batch, rep, not preds_only)
+    def forward_rows(self, batch: torch.Tensor, rep: int = 1, preds_only: bool = True, first_row: int = 0):
+        logits, purified = self._run(batch, rep, not preds_only, first_row=first_row)
         return logits if preds_only else (logits, purified)
 
     @torch.no_grad()

@@ -112,9 +112,9 @@ class E4EStyleGanDefenseModel(MLVGMDefenseModel, torch.nn.Module):
         return eng.build_e4e_defense(ae.encoder_sd, ae.encoder_spec, ae.decoder_sd, ae.decoder_spec, ae.latent_avg,
                                      clf.state_dict, clf.spec, pool_to=min(256, size))
 
-    def forward_rows(self, batch: torch.Tensor, rep: int = 1, preds_only: bool = True):
+    def forward_rows(self, batch: torch.Tensor, rep: int = 1, preds_only: bool = True, first_row: int = 0):
         self.image_size = batch.shape[-1]
-        return super().forward_rows(batch, rep, preds_only)
+        return super().forward_rows(batch, rep, preds_only, first_row)
 
     def forward_candidates(self, batch: torch.Tensor, alphas, rep: int = 1, preds_only: bool = True):
         self.image_size = batch.shape[-1]
@@ -165,9 +165,9 @@ class TransStyleGanDefenseModel(MLVGMDefenseModel, torch.nn.Module):
         return eng.build_trans_defense(ae.encoder_sd, ae.encoder_spec, ae.decoder_sd, ae.decoder_spec, ae.latent_avg,
                                        clf.state_dict, clf.spec, pool_to=min(res, ae.decoder_spec.size), mid=2 * res, crop=res // 4)
 
-    def forward_rows(self, batch: torch.Tensor, rep: int = 1, preds_only: bool = True):
+    def forward_rows(self, batch: torch.Tensor, rep: int = 1, preds_only: bool = True, first_row: int = 0):
         self.image_size = batch.shape[-1]
-        return super().forward_rows(batch, rep, preds_only)
+        return super().forward_rows(batch, rep, preds_only, first_row)
 
     def forward_candidates(self, batch: torch.Tensor, alphas, rep: int = 1, preds_only: bool = True):
         self.image_size = batch.shape[-1]

@@ -600,6 +600,49 @@ int ga_interleave2(const ga_interleave2_desc* d, void* stream);
 int ga_axpby(const float* x, float* y, long n, float alpha, float beta, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * ga_randn — the defenders' N(0,1) draws (latent noise of every group, input noise: torch.randn_like in
+ * src/defenses/ours/abstract_models.py:132-138 and the purify() methods of models.py) from a counter-based generator: element e
+ * of absolute row R of tensor `tensor` at draw `draw` under `seed` is a pure function of (seed, draw, tensor, R, e), so a step's
+ * noise does not depend on how its rows are cut into chunks or spread over ranks, and a CPU restatement
+ * (gen_adversarial_amd/noise.py) gives the same numbers with nothing stored.  Not a plan op: it is called directly, before
+ * ga_plan_run.
+ *
+ * The numbers (the contract of noise.py):
+ *   - Philox4x32-10: per round  (hi0, lo0) = 0xD2511F53 * c0,  (hi1, lo1) = 0xCD9E8D57 * c2  (32 x 32 -> 64 bit),
+ *     c <- (hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0);  between rounds k0 += 0x9E3779B9, k1 += 0xBB67AE85;  ten rounds.
+ *     key = (seed & 0xffffffff, seed >> 32).
+ *   - quad q = e / 4 of row r uses the counter (q, (unsigned)(row0 + r), tensor, draw); its output words x0..x3 belong to
+ *     elements 4q .. 4q+3.
+ *   - uniforms u_k = ((x_k >> 9) + 0.5f) * 2^-23: exact in fp32, strictly inside (0, 1), smallest value 2^-24.
+ *   - normals, Box-Muller on the pairs (u0, u1) and (u2, u3):
+ *       z_{2j} = sqrt(-2 ln u_{2j}) * cos(2 pi u_{2j+1}),   z_{2j+1} = sqrt(-2 ln u_{2j}) * sin(2 pi u_{2j+1})
+ *     with the angle taken as sincospif(2 * u): 2 * u is exact, 2 pi u rounded to fp32 would cost ~1.4e-6 at the largest radius.
+ *     |z| <= sqrt(-2 ln 2^-24) = 5.768.
+ *   - y[r, e] = scale * z.
+ * With `coef`: coef[r] = coef_eps / sqrt(sum_e y[r,e]^2), the input-noise normalisation (abstract_models.py:136-138), as a
+ * two-stage sum without atomics (one partial per workgroup in ws, added in index order by a second launch: same bits every run).
+ * ws_floats >= rows * ceil(inner / 4 / 256).
+ * GA_E_BADARG: y NULL, rows <= 0, inner <= 0, row0 + rows > 2^32, mode not 0 / 1, coef without ws or with too small a ws;
+ * GA_E_UNSUPPORTED: inner % 4 != 0;  GA_E_ALIGN: y not 16-byte aligned.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define GA_RANDN_STREAM_INPUT 2147483648   /* the input noise; latent group i draws with tensor = i */
+/* Scalars, as ga_pixelnorm / ga_rep_sum / ga_axpby take them, on purpose: every typedef of this header is a plan op's descriptor
+ * (tests/test_abi_layout_cpu.py holds the header to that), and ga_randn is no plan op.  Mind the order of the neighbouring unsigned
+ * arguments: seed, draw, tensor, row0.
+ *   y          [rows, inner], written; inner % 4 == 0
+ *   seed       Philox key = (seed & 0xffffffff, seed >> 32)
+ *   draw       counter word 3
+ *   tensor     counter word 2: which tensor of the call (latent group i, or GA_RANDN_STREAM_INPUT)
+ *   row0       absolute row of y's first row; counter word 1 = (unsigned)(row0 + r); row0 + rows <= 2^32
+ *   scale      y = scale * z
+ *   mode       0: normals; 1: the raw 32-bit words, bit patterns stored in y (tests, C users); `scale` is not read then, and
+ *              `coef` is refused
+ *   coef, coef_eps   optional: coef[r] = coef_eps / sqrt(sum_e y[r,e]^2)
+ *   ws, ws_floats    partial sums of the two-stage reduction; required with coef */
+int ga_randn(float* y, long rows, long inner, unsigned long seed, unsigned draw, unsigned tensor, unsigned long row0, float scale,
+             int mode, float* coef, float coef_eps, float* ws, long ws_floats, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Plans: a forward or backward pass is a flat list of the ops above, built once on the host and replayed by ONE call.
  * ------------------------------------------------------------------------------------------------------------------ */
 typedef struct ga_axpby_desc { const float* x; float* y; long n; float alpha, beta; } ga_axpby_desc;
@@ -681,6 +724,8 @@ const char* ga_last_hip_error(void);
  * stays.) */
 /* (ga_sampler_desc.mode == 2 is a value ga_sampler_mix refused before, and ga_latent_mix_desc.backward was only ever set to 0 or 1:
  * a formerly refused or unused mode value changes no layout and no existing call, so the version stays.) */
+/* (ga_randn is an entry point of its own beside the plan: no descriptor and not ga_op changes, and the binding
+ * looks every declared symbol up when it loads, so a library built before ga_randn existed is refused by name: the version stays.) */
 #define GA_ABI_VERSION 8
 int ga_abi_version(void);
 unsigned long ga_sizeof_op(void);
