@@ -80,6 +80,38 @@ def dry_engines():
 
 
 # ---------------------------------------------------------------------------------------------------- on a device
+def nvae_variants(dev, first, model, eot=32, big=512):
+    """(name, build) of the configs[1] NVAE + VGG plans bench.py builds and times beside its 1024-row chunk plan: the `big`-row
+    (16 images) and the eot-row (1 image, the reference protocol) plans, the same two with the encoder shared by the EoT replicas
+    (addend_rep > 1), the K-cotangent class-Jacobian plans of bench.class_jacobian_measurement (share_encoder, noise_eps 0.0,
+    cot_rep = K: K = 16 at one image, K = 4 at 16 images; dact_rep > 1) and the fp32 secondary at eot rows.
+
+    `first`, `model` are what bench.build_model returned for the chunk plan (of `first` only rep, noise_eps and the WeightStore are
+    read: the engine itself may be gone).  Each variant is bench.clone_engine's Engine call, the one build_model makes, over that
+    model and that store: build_model itself draws the state dicts again on every call (9 s each where this was measured, against
+    under 0.1 s for an engine; the plans hold the same descriptors either way), and nothing is folded or split twice.  Real engines
+    on `dev`, built when `build` is called."""
+    from types import SimpleNamespace as NS
+    from bench import clone_engine
+    from gen_adversarial_amd.engine import Engine
+    from gen_adversarial_amd.nvae_spec import ASSUMED_NVAE_CONFIG, ASSUMED_NVAE_RESOLUTION
+
+    def plain(rows, precision='bf16x3', share_encoder=False):
+        like = NS(rows=rows, rep=eot, noise_eps=first.noise_eps, store=first.store)
+        return clone_engine(like, model, dev, NS(precision=precision, share_encoder=share_encoder))
+
+    def jacobian(rows, K):
+        sd, vsd, vspec, alphas = model
+        return Engine(sd, ASSUMED_NVAE_CONFIG, ASSUMED_NVAE_RESOLUTION, vsd, vspec, rows=rows, rep=eot, alphas=alphas, temperature=0.6,
+                      noise_eps=0.0, device=dev, precision='bf16x3', share_encoder=True, store=first.store, cot_rep=K)
+    for rows in (big, eot):
+        yield f'nvae.{rows}', lambda r=rows: plain(r)
+        yield f'nvae.{rows}.shared', lambda r=rows: plain(r, share_encoder=True)
+    yield f'nvae.{eot}.shared.K16', lambda: jacobian(eot, 16)
+    yield f'nvae.{big}.shared.K4', lambda: jacobian(big, 4)
+    yield f'nvae.{eot}.fp32', lambda: plain(eot, precision='fp32')
+
+
 def device_engines(dev, dry_run=False):
     """(name, build) of the reduced engines the GPU tests build beside the benchmarked ones: the ND-VAE and A-VAE defenders of
     tests/test_competitors_gpu.py, the K-cotangent engines of tests/test_competitor_class_jacobian_gpu.py and
