@@ -19,6 +19,7 @@
 //     3-channel image) run on the exact fp32-MFMA kernel.
 #include "conv_split.h"
 #include "conv_epilogue.h"
+#include "conv_families.h"
 
 namespace ga {
 
@@ -313,8 +314,8 @@ static void launch_bf3_inst(const ga_conv_desc& d, hipStream_t stream, dim3 grid
     X(0x021, 2, GA_ACT_SILU, false)
 static inline int conv_bf3_mode(const ga_conv_desc& d) { return ((d.C2 > 0 ? 1 : 0) << 8) | conv_pro_mode(d); }
 
-// 1 when conv_bf3 has a kernel for this descriptor's prologue (ga_conv2d falls back to the fp32 kernel otherwise)
-int conv_bf3_supports(const ga_conv_desc& d) {
+// 1 when conv_bf3 has a kernel for this descriptor's prologue: part of ga_conv2d's `bf3`, which every split-bf16 family requires
+int conv_bf3_mode_ok(const ga_conv_desc& d) {
     switch (conv_bf3_mode(d)) {
         GA_BF3_MODES(GA_MODE_CASE) return 1;
         default: return 0;
@@ -324,17 +325,12 @@ int conv_bf3_supports(const ga_conv_desc& d) {
 template <int WM, int WN, int TM, int TN>
 static int launch_bf3(const ga_conv_desc& d, hipStream_t stream, int vec_out, int splits) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-    const int M = d.N * d.Ho * d.Wo;
     const int Ctot = d.C1 + d.C2;
     const int Ktot = d.KH * d.KW * Ctot;
     const int nkc = (Ctot + BK3 - 1) / BK3;
-    const int tilesM = (M + BM - 1) / BM, tilesN = (d.Cout + BN - 1) / BN;
-    size_t lds = (size_t)2 * (2 * BM + 2 * BN) * LDB * 2;
-    const size_t lds_c = (size_t)BM * (BN + 4) * sizeof(float);
-    if (lds_c > lds) lds = lds_c;
-    const dim3 grid(tilesM * tilesN, splits);
+    const conv_tiling t = conv_tile_grid(d, BM, BN, splits, (size_t)2 * (2 * BM + 2 * BN) * LDB * 2);
 #define GA_BF3(MODE, A, C, D) \
-    case MODE: launch_bf3_inst<WM, WN, TM, TN, A, C, D>(d, stream, grid, lds, tilesN, M, Ctot, Ktot, nkc, vec_out); break;
+    case MODE: launch_bf3_inst<WM, WN, TM, TN, A, C, D>(d, stream, t.grid, t.lds, t.tilesN, t.M, Ctot, Ktot, nkc, vec_out); break;
     switch (conv_bf3_mode(d)) {
         GA_BF3_MODES(GA_BF3)
         default: return GA_E_UNSUPPORTED;
@@ -343,8 +339,12 @@ static int launch_bf3(const ga_conv_desc& d, hipStream_t stream, int vec_out, in
     return check_launch();
 }
 
-// called by ga_conv2d (conv_mfma.hip) once the descriptor has been validated and the buffer extents filled in
-int conv_bf3_dispatch(const ga_conv_desc& d, hipStream_t stream, int tile, int vec_out, int splits) {
+// tile codes 1 - 4 on the split-bf16 operands; ga_conv2d runs the fp32 family's tile of the same code when this refuses
+int conv_bf3_check(const ga_conv_desc&, const conv_req& r) { return r.bf3 && r.tile >= 1 && r.tile <= 4 ? GA_OK : GA_E_UNSUPPORTED; }
+
+// (the quick experiment builds compile tile 1 only and refuse the others here, past check)
+int conv_bf3_launch(const ga_conv_desc& d, const conv_req& r, hipStream_t stream) {
+    const int tile = r.tile, vec_out = r.vec_out, splits = r.splits;
     switch (tile) {
         case 1: return launch_bf3<2, 2, 2, 2>(d, stream, vec_out, splits);
 #ifdef GA_TRACE_TILE1_ONLY      // quick experiment builds
@@ -359,16 +359,6 @@ int conv_bf3_dispatch(const ga_conv_desc& d, hipStream_t stream, int tile, int v
     }
 }
 
-// host helper exported for weight preparation: w (fp32, n elements) -> hi, lo (bf16 bit patterns)
-__global__ void split_bf16_kernel(const float* w, __bf16* hi, __bf16* lo, const long n) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const float v = w[i];
-        const __bf16 h = (__bf16)v;
-        hi[i] = h;
-        lo[i] = (__bf16)(v - (float)h);
-    }
-}
-
 }  // namespace ga
 
 #ifdef GA_TRACE
@@ -376,13 +366,3 @@ extern "C" int ga_debug_trace_read(unsigned long long* out, int n) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(ga::ga_trace_buf), (size_t)n * 8) == hipSuccess ? GA_OK : GA_E_LAUNCH;
 }
 #endif
-
-extern "C" int ga_split_bf16(const float* w, void* hi, void* lo, long n, void* stream) {
-    ga::clear_stale_error();
-    if (!w || !hi || !lo || n <= 0) return GA_E_BADARG;
-    long blocks = (n + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(ga::split_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w,
-                       (__bf16*)hi, (__bf16*)lo, n);
-    return ga::check_launch();
-}

@@ -15,6 +15,7 @@
 // instead of 9, hence a second set of instantiations (template parameter RP).
 #include "conv_split.h"
 #include "conv_epilogue.h"
+#include "conv_families.h"
 
 namespace ga {
 
@@ -532,8 +533,8 @@ static void launch_halo_bd_inst(const ga_conv_desc& d, hipStream_t stream, dim3 
 }
 
 // 1 when the descriptor is a 3x3 / stride 1 / pad 1 single-source convolution whose 128-pixel tiles are whole image rows
-// (or whole small images) or 128-pixel segments of one row
-int conv_halo3_supports(const ga_conv_desc& d) {
+// (or whole small images) or 128-pixel segments of one row, with a prologue of GA_CONV3_MODES
+int conv_halo3_shape_ok(const ga_conv_desc& d) {
     if (d.KH != 3 || d.KW != 3 || d.sn != 1 || d.sd != 1 || d.pad != 1 || d.C2 != 0) return 0;
     if (d.Ho != d.Hi || d.Wo != d.Wi || d.C1 % HK != 0) return 0;
     const int HoWo = d.Ho * d.Wo;
@@ -569,28 +570,68 @@ static int halo_geometry(const ga_conv_desc& d, const int BM, halo_geom& g, cons
     return GA_OK;
 }
 
-template <int WM, int WN, int TM, int TN>
-static int launch_halo(const ga_conv_desc& d, hipStream_t stream, int vec_out, int splits) {
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-    const int M = d.N * d.Ho * d.Wo;
-    const int Ktot = 9 * d.C1;
-    const int nkc = d.C1 / HK;
+// tiles 5 - 7 also have the 13-slot row-segment kernel for this prologue (the WIDE entries of GA_CONV3_MODES)
+static bool halo_mode_wide(const ga_conv_desc& d) {
+#define GA_HALO_WIDE(MODE, A, C, WIDE) case MODE: return WIDE;
+    switch (conv_pro_mode(d)) {
+        GA_CONV3_MODES(GA_HALO_WIDE)
+        default: return false;
+    }
+#undef GA_HALO_WIDE
+}
+
+// What a launch of tile 5 - 8 is made of beyond the descriptor.  halo_plan_for computes it for check and launch alike and refuses
+// what does not fit: more patch pixels than the kernels have slots for, split-K finer than the channel chunks, too much LDS.
+struct halo_plan {
     halo_geom g;
-    { const int rc = halo_geometry(d, BM, g); if (rc != GA_OK) return rc; }
-    if (splits > nkc) return GA_E_UNSUPPORTED;
-    const int tilesM = (M + BM - 1) / BM, tilesN = (d.Cout + BN - 1) / BN;
-    size_t lds = ((size_t)2 * g.NI * g.IS + (size_t)2 * 2 * BN * LDH) * 2;
-    if (lds > 160 * 1024) return GA_E_UNSUPPORTED;
-    const size_t lds_c = (size_t)BM * (BN + 4) * sizeof(float);
-    if (lds_c > lds) lds = lds_c;
-    const dim3 grid(tilesM * tilesN, splits);
-    // row-segment tiles (13 patch slots) exist for the WIDE entries of the list only
-    const bool wide = g.P > 9 * 32;
-#define GA_HALO(MODE, A, C, WIDE)                                                                                                    \
-    case MODE:                                                                                                                       \
-        if (!wide) launch_halo_inst<WM, WN, TM, TN, A, C, 9>(d, stream, grid, lds, tilesN, M, Ktot, nkc, vec_out, g);                \
-        else if constexpr (WIDE) launch_halo_inst<WM, WN, TM, TN, A, C, 13>(d, stream, grid, lds, tilesN, M, Ktot, nkc, vec_out, g); \
-        else return GA_E_UNSUPPORTED;                                                                                                \
+    conv_tiling t;
+    int nkc;                    // 32-channel chunks
+    int dbuf, tab_off;          // tile 8: the patch is double-buffered; float offset of the slot / prologue tables in LDS
+};
+static int halo_plan_for(const ga_conv_desc& d, const conv_req& r, halo_plan& p) {
+    constexpr int BM = 128;
+    const int BN = r.tile == 6 ? 64 : r.tile == 7 ? 32 : 128;       // 5: 128 x 128, 6: 128 x 64, 7: 128 x 32, 8: 128 x 128
+    if (r.tile == 8 && (!d.w_frag || !aligned16(d.w_frag))) return GA_E_UNSUPPORTED;
+    p.nkc = d.C1 / HK;
+    { const int rc = halo_geometry(d, BM, p.g); if (rc != GA_OK) return rc; }
+    const halo_geom& g = p.g;
+    if (r.splits > p.nkc) return GA_E_UNSUPPORTED;
+    if (r.tile != 8) {
+        const size_t lds = ((size_t)2 * g.NI * g.IS + (size_t)2 * 2 * BN * LDH) * 2;
+        if (lds > 160 * 1024) return GA_E_UNSUPPORTED;
+        // row-segment tiles (13 patch slots) exist for the WIDE entries of the list only
+        if (g.P > 9 * 32 && !halo_mode_wide(d)) return GA_E_UNSUPPORTED;
+        p.dbuf = p.tab_off = 0;
+        p.t = conv_tile_grid(d, BM, BN, r.splits, lds);
+        return GA_OK;
+    }
+    const size_t patch = (size_t)2 * g.NI * g.IS * 2;                   // hi + lo planes of one buffer, bytes
+    const int mode = conv_pro_mode(d);
+    const int rp = (g.P * 8 + 255) >> 8;                                // patch slots per thread
+    const size_t tab = (size_t)rp * 256 * 6                             // slot tables: global offsets (int) + LDS offsets (short)
+                       + (mode >= 0x10 ? (size_t)2 * (mode == 0x20 ? g.NI : 1) * d.C1 * sizeof(float) : 0);      // prologue table
+    p.dbuf = 2 * patch + tab <= 80 * 1024 ? 1 : 0;                      // two buffers when two workgroups per CU still fit
+    p.tab_off = (int)(((p.dbuf ? 2 : 1) * patch + 15) / 16 * 4);        // floats, 16-byte aligned
+    const size_t lds = (size_t)p.tab_off * 4 + tab;
+    if (lds > 80 * 1024) return GA_E_UNSUPPORTED;                       // (two workgroups per CU are the kernel's launch bounds)
+    // (r04 experiment, dropped: asking for > 80 KB of LDS so that a launch takes ONE workgroup slot per CU and the second slot goes to
+    // the other stream's kernel — out of phase, so that one's setup / epilogue would overlap the other's K loop: 5,579 against 5,949 -
+    // 5,967 rows/s on the same box, gpurun_out/r04_ab_epi.log: a lone conv launch then runs at half occupancy)
+    if (g.P > 9 * 32) return GA_E_UNSUPPORTED;                          // row-segment tiles of wide images: the LDS-staged kernel
+    p.t = conv_tile_grid(d, BM, BN, r.splits, lds);
+    return GA_OK;
+}
+
+template <int WM, int WN, int TM, int TN>
+static int launch_halo(const ga_conv_desc& d, hipStream_t stream, const int vec_out, const halo_plan& p) {
+    const conv_tiling& t = p.t;
+    const int Ktot = 9 * d.C1;
+    const bool wide = p.g.P > 9 * 32;
+#define GA_HALO(MODE, A, C, WIDE)                                                                                                          \
+    case MODE:                                                                                                                             \
+        if (!wide) launch_halo_inst<WM, WN, TM, TN, A, C, 9>(d, stream, t.grid, t.lds, t.tilesN, t.M, Ktot, p.nkc, vec_out, p.g);          \
+        else if constexpr (WIDE) launch_halo_inst<WM, WN, TM, TN, A, C, 13>(d, stream, t.grid, t.lds, t.tilesN, t.M, Ktot, p.nkc, vec_out, p.g); \
+        else return GA_E_UNSUPPORTED;                                                                                                      \
         break;
     switch (conv_pro_mode(d)) {
         GA_CONV3_MODES(GA_HALO)
@@ -600,34 +641,11 @@ static int launch_halo(const ga_conv_desc& d, hipStream_t stream, int vec_out, i
     return check_launch();
 }
 
-static int launch_halo_bd(const ga_conv_desc& d, hipStream_t stream, int vec_out, int splits) {
-    constexpr int BM = 128, BN = 128;
-    if (!d.w_frag || !aligned16(d.w_frag)) return GA_E_UNSUPPORTED;
-    const int M = d.N * d.Ho * d.Wo;
-    const int nkc = d.C1 / HK;
-    halo_geom g;
-    { const int rc = halo_geometry(d, BM, g); if (rc != GA_OK) return rc; }
-    if (splits > nkc) return GA_E_UNSUPPORTED;
-    const int tilesM = (M + BM - 1) / BM, tilesN = (d.Cout + BN - 1) / BN;
-    const size_t patch = (size_t)2 * g.NI * g.IS * 2;                   // hi + lo planes of one buffer, bytes
-    const int mode = conv_pro_mode(d);
-    const int rp = (g.P * 8 + 255) >> 8;                                // patch slots per thread
-    const size_t tab = (size_t)rp * 256 * 6                             // slot tables: global offsets (int) + LDS offsets (short)
-                       + (mode >= 0x10 ? (size_t)2 * (mode == 0x20 ? g.NI : 1) * d.C1 * sizeof(float) : 0);      // prologue table
-    const int dbuf = 2 * patch + tab <= 80 * 1024 ? 1 : 0;              // two buffers when two workgroups per CU still fit
-    const int tab_off = (int)(((dbuf ? 2 : 1) * patch + 15) / 16 * 4);  // floats, 16-byte aligned
-    size_t lds = (size_t)tab_off * 4 + tab;
-    if (lds > 80 * 1024) return GA_E_UNSUPPORTED;                       // (two workgroups per CU are the kernel's launch bounds)
-    const size_t lds_c = (size_t)BM * (BN + 4) * sizeof(float);
-    if (lds_c > lds) lds = lds_c;
-    // (r04 experiment, dropped: asking for > 80 KB of LDS so that a launch takes ONE workgroup slot per CU and the second slot goes to
-    // the other stream's kernel — out of phase, so that one's setup / epilogue would overlap the other's K loop: 5,579 against 5,949 -
-    // 5,967 rows/s on the same box, gpurun_out/r04_ab_epi.log: a lone conv launch then runs at half occupancy)
-    const dim3 grid(tilesM * tilesN, splits);
-    if (g.P > 9 * 32) return GA_E_UNSUPPORTED;                          // row-segment tiles of wide images: the LDS-staged kernel
+static int launch_halo_bd(const ga_conv_desc& d, hipStream_t stream, const int vec_out, const halo_plan& p) {
+    const conv_tiling& t = p.t;
 #define GA_HBD(MODE, A, C, WIDE) \
-    case MODE: launch_halo_bd_inst<A, C, 9>(d, stream, grid, lds, tilesN, M, nkc, vec_out, g, dbuf, tab_off); break;
-    switch (mode) {
+    case MODE: launch_halo_bd_inst<A, C, 9>(d, stream, t.grid, t.lds, t.tilesN, t.M, p.nkc, vec_out, p.g, p.dbuf, p.tab_off); break;
+    switch (conv_pro_mode(d)) {
 #ifdef GA_HALO_EXP_ONLY     // quick experiment builds (make hexp): two prologues only
         GA_CONV3_MODES_EXP(GA_HBD)
 #else
@@ -640,14 +658,22 @@ static int launch_halo_bd(const ga_conv_desc& d, hipStream_t stream, int vec_out
 }
 
 // tile codes 5 (128 x 128), 6 (128 x 64) and 7 (128 x 32) of ga_conv_desc.tile, 8 = 128 x 128 with the weight fragments read from
-// global memory (needs w_frag); called by ga_conv2d after validation
-int conv_halo3_dispatch(const ga_conv_desc& d, hipStream_t stream, int tile, int vec_out, int splits) {
-    switch (tile) {
-        case 8: return launch_halo_bd(d, stream, vec_out, splits);
+// global memory (needs w_frag in the tile-8 order): split-bf16 operands, vector output, the shape, and a plan that fits
+int conv_halo3_check(const ga_conv_desc& d, const conv_req& r) {
+    if (r.tile < 5 || r.tile > 8 || !(r.bf3 && r.vec_out && conv_halo3_shape_ok(d))) return GA_E_UNSUPPORTED;
+    halo_plan p;
+    return halo_plan_for(d, r, p);
+}
+
+int conv_halo3_launch(const ga_conv_desc& d, const conv_req& r, hipStream_t stream) {
+    halo_plan p;
+    { const int rc = halo_plan_for(d, r, p); if (rc != GA_OK) return rc; }
+    switch (r.tile) {
+        case 8: return launch_halo_bd(d, stream, r.vec_out, p);
 #ifndef GA_HALO_EXP_ONLY    // (make hexp: tile 8 alone)
-        case 5: return launch_halo<2, 2, 2, 2>(d, stream, vec_out, splits);
-        case 6: return launch_halo<4, 1, 1, 2>(d, stream, vec_out, splits);
-        case 7: return launch_halo<4, 1, 1, 1>(d, stream, vec_out, splits);
+        case 5: return launch_halo<2, 2, 2, 2>(d, stream, r.vec_out, p);
+        case 6: return launch_halo<4, 1, 1, 2>(d, stream, r.vec_out, p);
+        case 7: return launch_halo<4, 1, 1, 1>(d, stream, r.vec_out, p);
 #endif
         default: return GA_E_UNSUPPORTED;
     }

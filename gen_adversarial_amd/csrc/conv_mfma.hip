@@ -1,4 +1,5 @@
-// ga_conv2d — fp32 implicit-GEMM convolution on the CDNA4 matrix cores (v_mfma_f32_32x32x2_f32).
+// conv_mfma — fp32 implicit-GEMM convolution on the CDNA4 matrix cores (v_mfma_f32_32x32x2_f32): the family that takes every
+// descriptor ga_conv2d (conv2d.hip) has validated, tile codes 1 - 4.
 //
 // GEMM view: C[M = N*Ho*Wo pixels][Cout] = A[M][K = taps*(C1+C2)] * B[K][Cout].
 //   * A is gathered on the fly from the NHWC activation (im2col never materialised); the prologue
@@ -16,10 +17,11 @@
 //     consecutive channels of one pixel: bias / act' (reads the saved forward input) / addends / store are all 16-B
 //     accesses on 512-B contiguous rows.  A scalar epilogue remains for channel counts that are not multiples of 4.
 //   * Split-K (small M x Cout with a long K: samplers, the classifier head): grid.y = splits, raw partial tiles go to
-//     a caller-provided workspace and a second kernel sums them in a fixed order and applies the epilogue.
+//     a caller-provided workspace and a second kernel (conv2d.hip) sums them in a fixed order and applies the epilogue.
 //   * blockIdx is remapped so that consecutive logical tiles (which share the A panel) run on one XCD's L2.
 #include "conv_split.h"
 #include "conv_epilogue.h"
+#include "conv_families.h"
 
 namespace ga {
 
@@ -358,27 +360,6 @@ conv_mfma_kernel(const ga_conv_desc d, const int tilesN, const int M, const int 
     conv_epilogue<WM, WN, TM, TN>(d, acc, smem, m0, n0, M, vec_out, splits, split);
 }
 
-// sums the split-K partial tiles in split order (bitwise reproducible) and applies the epilogue
-__global__ void __launch_bounds__(256) conv_splitk_reduce_kernel(const ga_conv_desc d, const int M, const int splits, const int vec_out) {
-    const int HoWo = d.Ho * d.Wo;
-    const size_t slab = (size_t)M * d.Cout;
-    if (vec_out) {
-        const long total4 = (long)slab / 4;
-        const int C4 = d.Cout / 4;
-        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long)gridDim.x * 256) {
-            floatx4 v = *reinterpret_cast<const floatx4*>(d.ws + i * 4);
-            for (int s = 1; s < splits; ++s) v += *reinterpret_cast<const floatx4*>(d.ws + s * slab + i * 4);
-            epilogue4(d, (int)(i / C4), (int)(i % C4) * 4, v, HoWo);
-        }
-    } else {
-        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < (long)slab; i += (long)gridDim.x * 256) {
-            float v = d.ws[i];
-            for (int s = 1; s < splits; ++s) v += d.ws[s * slab + i];
-            epilogue1(d, (int)(i / d.Cout), (int)(i % d.Cout), v, HoWo);
-        }
-    }
-}
-
 template <int WM, int WN, int TM, int TN, bool VEC, int PRO, bool FAST>
 static void launch_inst(const ga_conv_desc& d, hipStream_t stream, dim3 grid, size_t lds, int tilesN, int M, int Ctot,
                         int Ktot, int nkc, int vec_out) {
@@ -388,191 +369,42 @@ static void launch_inst(const ga_conv_desc& d, hipStream_t stream, dim3 grid, si
                        make_fastdiv(d.Ho * d.Wo), make_fastdiv(d.Wo));
 }
 
+
 template <int WM, int WN, int TM, int TN>
 static int launch_conv(const ga_conv_desc& d, hipStream_t stream, bool vec, int vec_out, int splits) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-    const int M = d.N * d.Ho * d.Wo;
     const int Ctot = d.C1 + d.C2;
     const int Ktot = d.KH * d.KW * Ctot;
     const int nkc = (Ctot + BK - 1) / BK;
-    const int tilesM = (M + BM - 1) / BM, tilesN = (d.Cout + BN - 1) / BN;
-    size_t lds = (size_t)2 * (BM + BN) * LDK * sizeof(float);
-    const size_t lds_c = (size_t)BM * (BN + 4) * sizeof(float);
-    if (lds_c > lds) lds = lds_c;
-    const dim3 grid(tilesM * tilesN, splits);
+    const conv_tiling t = conv_tile_grid(d, BM, BN, splits, (size_t)2 * (BM + BN) * LDK * sizeof(float));
     const int pro = d.pro_scale && d.pro_per_row ? 2 : ((d.pro_scale || d.pro_act) ? 1 : 0);
     const bool fast = vec && d.sd == 1 && (d.C2 == 0 || d.C1 % BK == 0) && d.KH * d.KW <= 32 &&
                       d.x_bytes > 0 && d.w_bytes > 0 && (d.C2 == 0 || d.x2_bytes > 0);
     if (fast) {
-        if (pro == 0) launch_inst<WM, WN, TM, TN, true, 0, true>(d, stream, grid, lds, tilesN, M, Ctot, Ktot, nkc, vec_out);
-        else if (pro == 1) launch_inst<WM, WN, TM, TN, true, 1, true>(d, stream, grid, lds, tilesN, M, Ctot, Ktot, nkc, vec_out);
-        else launch_inst<WM, WN, TM, TN, true, 2, true>(d, stream, grid, lds, tilesN, M, Ctot, Ktot, nkc, vec_out);
+        if (pro == 0) launch_inst<WM, WN, TM, TN, true, 0, true>(d, stream, t.grid, t.lds, t.tilesN, t.M, Ctot, Ktot, nkc, vec_out);
+        else if (pro == 1) launch_inst<WM, WN, TM, TN, true, 1, true>(d, stream, t.grid, t.lds, t.tilesN, t.M, Ctot, Ktot, nkc, vec_out);
+        else launch_inst<WM, WN, TM, TN, true, 2, true>(d, stream, t.grid, t.lds, t.tilesN, t.M, Ctot, Ktot, nkc, vec_out);
     } else if (vec) {
-        if (pro == 0) launch_inst<WM, WN, TM, TN, true, 0, false>(d, stream, grid, lds, tilesN, M, Ctot, Ktot, nkc, vec_out);
-        else if (pro == 1) launch_inst<WM, WN, TM, TN, true, 1, false>(d, stream, grid, lds, tilesN, M, Ctot, Ktot, nkc, vec_out);
-        else launch_inst<WM, WN, TM, TN, true, 2, false>(d, stream, grid, lds, tilesN, M, Ctot, Ktot, nkc, vec_out);
+        if (pro == 0) launch_inst<WM, WN, TM, TN, true, 0, false>(d, stream, t.grid, t.lds, t.tilesN, t.M, Ctot, Ktot, nkc, vec_out);
+        else if (pro == 1) launch_inst<WM, WN, TM, TN, true, 1, false>(d, stream, t.grid, t.lds, t.tilesN, t.M, Ctot, Ktot, nkc, vec_out);
+        else launch_inst<WM, WN, TM, TN, true, 2, false>(d, stream, t.grid, t.lds, t.tilesN, t.M, Ctot, Ktot, nkc, vec_out);
     } else {
-        launch_inst<WM, WN, TM, TN, false, 1, false>(d, stream, grid, lds, tilesN, M, Ctot, Ktot, nkc, vec_out);
+        launch_inst<WM, WN, TM, TN, false, 1, false>(d, stream, t.grid, t.lds, t.tilesN, t.M, Ctot, Ktot, nkc, vec_out);
     }
     return check_launch();
 }
 
-int conv_bf3_dispatch(const ga_conv_desc& d, hipStream_t stream, int tile, int vec_out, int splits);   // conv_bf3.hip
-int conv_bf3_supports(const ga_conv_desc& d);
-int conv_halo3_dispatch(const ga_conv_desc& d, hipStream_t stream, int tile, int vec_out, int splits);  // conv_halo3.hip
-int conv_halo3_supports(const ga_conv_desc& d);
-int conv_quad3_dispatch(const ga_conv_desc& d, hipStream_t stream, int vec_out, int splits);             // conv_quad3.hip
-int conv_quad3_supports(const ga_conv_desc& d, int splits);
-int conv_thin3_dispatch(const ga_conv_desc& d, hipStream_t stream, int vec_out, int splits);             // conv_thin3.hip
-int conv_thin3_supports(const ga_conv_desc& d);
-int conv_pw_frag_dispatch(const ga_conv_desc& d, hipStream_t stream, int vec_out);                       // conv_pw_frag.hip
-int conv_pw_frag_supports(const ga_conv_desc& d, int splits);
+// tile codes 1 (128 x 128), 2 (128 x 64), 3 (64 x 64) and 4 (128 x 32): every validated descriptor, whatever its operands
+int conv_mfma_check(const ga_conv_desc&, const conv_req& r) { return r.tile >= 1 && r.tile <= 4 ? GA_OK : GA_E_UNSUPPORTED; }
+
+int conv_mfma_launch(const ga_conv_desc& d, const conv_req& r, hipStream_t stream) {
+    switch (r.tile) {
+        case 1: return launch_conv<2, 2, 2, 2>(d, stream, r.vec, r.vec_out, r.splits);
+        case 2: return launch_conv<4, 1, 1, 2>(d, stream, r.vec, r.vec_out, r.splits);
+        case 3: return launch_conv<2, 2, 1, 1>(d, stream, r.vec, r.vec_out, r.splits);
+        case 4: return launch_conv<4, 1, 1, 1>(d, stream, r.vec, r.vec_out, r.splits);
+        default: return GA_E_UNSUPPORTED;
+    }
+}
 
 }  // namespace ga
-
-// byte extent of one operand above which ga_conv2d convolves row sub-batches (the fast loaders' 31-bit offsets); lowered by
-// ga_debug_set_conv_row_limit so that tests reach the sub-batch path at small sizes
-static long g_conv_row_limit = 0x7fffff00L;
-static long ga_conv_row_limit() { return g_conv_row_limit; }
-extern "C" long ga_debug_set_conv_row_limit(long bytes) {
-    const long old = g_conv_row_limit;
-    g_conv_row_limit = bytes > 0 ? bytes : 0x7fffff00L;
-    return old;
-}
-
-extern "C" int ga_conv2d(const ga_conv_desc* dp, void* stream_) {
-    ga::clear_stale_error();
-    using namespace ga;
-    if (!dp) return GA_E_BADARG;
-    const ga_conv_desc& d = *dp;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    if (!d.x || !d.w || !d.y) return GA_E_BADARG;
-    if (d.N <= 0 || d.Hi <= 0 || d.Wi <= 0 || d.C1 <= 0 || d.C2 < 0 || d.Ho <= 0 || d.Wo <= 0 || d.Cout <= 0) return GA_E_BADARG;
-    if (d.KH <= 0 || d.KW <= 0 || d.sn <= 0 || d.sd <= 0 || d.pad < 0) return GA_E_BADARG;
-    if (d.sd & (d.sd - 1)) return GA_E_UNSUPPORTED;          // transposed stride must be a power of two
-    if (d.C2 > 0 && !d.x2) return GA_E_BADARG;
-    if ((d.pro_scale == nullptr) != (d.pro_shift == nullptr)) return GA_E_BADARG;
-    if (d.dact_x && ((d.dact_scale == nullptr) != (d.dact_shift == nullptr))) return GA_E_BADARG;
-    if (d.ldx < d.C1 || (d.C2 > 0 && d.ldx2 < d.C2) || d.ldy < d.Cout) return GA_E_BADARG;
-    if (d.addend && d.ldadd < d.Cout) return GA_E_BADARG;
-    if (d.addend2 && d.ldadd2 < d.Cout) return GA_E_BADARG;
-    if (d.dact_x && d.lddact < d.Cout) return GA_E_BADARG;
-    if (d.dact_x && d.dact_rep > 1 && d.N % d.dact_rep) return GA_E_BADARG;
-    // Rows are independent: a tensor beyond the fast loader's 31-bit byte offsets (2 GB; StyleGAN2's 1024^2 x 32-channel maps
-    // at a few dozen rows) is convolved in sub-batches of rows that fit, each an ordinary launch on the same stream.
-    {
-        const long row_x = (long)d.Hi * d.Wi * d.ldx * 4, row_x2 = d.C2 > 0 ? (long)d.Hi * d.Wi * d.ldx2 * 4 : 0;
-        long row_max = row_x > row_x2 ? row_x : row_x2;
-        const long pix_out = (long)d.Ho * d.Wo * 4;          // every per-row operand counts: output, addends, act' source
-        if (pix_out * d.ldy > row_max) row_max = pix_out * d.ldy;
-        if (d.addend && !d.addend_bcast_n && pix_out * d.ldadd > row_max) row_max = pix_out * d.ldadd;
-        if (d.addend2 && pix_out * d.ldadd2 > row_max) row_max = pix_out * d.ldadd2;
-        if (d.dact_x && pix_out * d.lddact > row_max) row_max = pix_out * d.lddact;
-        const long lim = ga_conv_row_limit();
-        if (d.N > 1 && row_max * d.N >= lim && row_max < lim) {
-            int sub = (int)((lim - 1) / row_max);
-            const int arep = d.addend && !d.addend_bcast_n && d.addend_rep > 1 ? d.addend_rep : 1;
-            const int drep = d.dact_x && d.dact_rep > 1 ? d.dact_rep : 1;
-            if (arep > 1 || drep > 1) {                      // operands shared by consecutive rows: cut at their row boundaries
-                const long both = (long)arep * drep;         // (a common multiple; the two never meet on one launch in practice)
-                if (d.N % arep || d.N % drep) return GA_E_BADARG;
-                sub -= (int)(sub % both);
-                if (sub < both) return GA_E_UNSUPPORTED;
-            }
-            for (int n0 = 0; n0 < d.N; n0 += sub) {
-                ga_conv_desc s = d;
-                s.N = d.N - n0 < sub ? d.N - n0 : sub;
-                const size_t pin = (size_t)n0 * d.Hi * d.Wi, pout = (size_t)n0 * d.Ho * d.Wo;
-                s.x = d.x + pin * d.ldx;
-                if (d.x2) s.x2 = d.x2 + pin * d.ldx2;
-                s.y = d.y + pout * d.ldy;
-                if (d.addend && !d.addend_bcast_n) s.addend = d.addend + (size_t)(n0 / arep) * d.Ho * d.Wo * d.ldadd;
-                if (d.addend2) s.addend2 = d.addend2 + pout * d.ldadd2;
-                if (d.dact_x) s.dact_x = d.dact_x + (size_t)(n0 / drep) * d.Ho * d.Wo * d.lddact;
-                if (d.pro_scale && d.pro_per_row) {
-                    s.pro_scale = d.pro_scale + (size_t)n0 * d.C1;
-                    s.pro_shift = d.pro_shift + (size_t)n0 * d.C1;
-                }
-                const int rc = ga_conv2d(&s, stream_);
-                if (rc != GA_OK) return rc;
-            }
-            return GA_OK;
-        }
-    }
-    if ((long)d.N * d.Ho * d.Wo > 0x7fffffffL) return GA_E_UNSUPPORTED;
-    if ((long)d.KH * d.KW * (d.C1 + d.C2) > 0x7fffffffL) return GA_E_UNSUPPORTED;
-    const long M = (long)d.N * d.Ho * d.Wo;
-    int splits = d.splits <= 1 ? 1 : d.splits;
-    if (splits > 1) {
-        if (!d.ws || d.ws_floats < (long)splits * M * d.Cout) return GA_E_BADARG;
-        const int T = d.KH * d.KW * ((d.C1 + d.C2 + 31) / 32);
-        if (splits > T) splits = T;
-        if (splits > 65535) return GA_E_UNSUPPORTED;
-    }
-
-    const bool vec = (d.C1 % 4 == 0) && (d.C2 % 4 == 0) && (d.ldx % 4 == 0) && (d.C2 == 0 || d.ldx2 % 4 == 0) &&
-                     aligned16(d.x) && aligned16(d.w) && (d.C2 == 0 || aligned16(d.x2)) &&
-                     (!d.pro_scale || (aligned16(d.pro_scale) && aligned16(d.pro_shift)));
-    const bool vec_out = (d.Cout % 4 == 0) && (d.ldy % 4 == 0) && aligned16(d.y) && (!d.bias || aligned16(d.bias)) &&
-                         (!d.addend || (d.ldadd % 4 == 0 && aligned16(d.addend))) &&
-                         (!d.addend2 || (d.ldadd2 % 4 == 0 && aligned16(d.addend2))) &&
-                         (!d.dact_x || (d.lddact % 4 == 0 && aligned16(d.dact_x) &&
-                                        (!d.dact_scale || (aligned16(d.dact_scale) && aligned16(d.dact_shift))))) &&
-                         (splits == 1 || aligned16(d.ws));
-
-    int tile = d.tile;
-    if (tile == 0) {
-        if (d.Cout <= 32) tile = 4;
-        else if (d.Cout <= 64) tile = (M >= 128 * 256) ? 2 : 3;
-        else {
-            const long b128 = ((M + 127) / 128) * ((d.Cout + 127) / 128);
-            const long b12864 = ((M + 127) / 128) * ((d.Cout + 63) / 64);
-            if (b128 >= 512) tile = 1;
-            else if (b12864 >= 512) tile = 2;
-            else tile = 3;
-        }
-    }
-    // buffer extents for the FAST loader (0 = tensor too large for 31-bit byte offsets -> generic loader)
-    ga_conv_desc k = d;
-    const long xb = ((long)d.N * d.Hi * d.Wi - 1) * d.ldx * 4 + (long)d.C1 * 4;
-    const long x2b = d.C2 > 0 ? ((long)d.N * d.Hi * d.Wi - 1) * d.ldx2 * 4 + (long)d.C2 * 4 : 0;
-    const long wb = (long)d.Cout * d.KH * d.KW * (d.C1 + d.C2) * 4;
-    const long lim = 0x7fffff00L;
-    k.x_bytes = xb < lim ? (unsigned)xb : 0;
-    k.x2_bytes = x2b < lim ? (unsigned)x2b : 0;
-    k.w_bytes = wb < lim ? (unsigned)wb : 0;
-    const int Ctot = d.C1 + d.C2;
-    const bool bf3 = d.w_hi && d.w_lo && vec && d.sd == 1 && (d.C2 == 0 || d.C1 % 32 == 0) && (Ctot % 8 == 0) &&
-                     d.KH * d.KW <= 32 && k.x_bytes > 0 && k.w_bytes > 0 && (d.C2 == 0 || k.x2_bytes > 0) &&
-                     aligned16(d.w_hi) && aligned16(d.w_lo) && conv_bf3_supports(d);
-    int rc;
-    if (tile == 11) {                   // persistent weights-resident 3x3 for 32 input channels (explicit request only; w_frag in the thin order)
-        if (!(bf3 && vec_out && conv_thin3_supports(d))) return GA_E_UNSUPPORTED;
-        rc = conv_thin3_dispatch(k, stream, vec_out, splits);
-    } else if (tile == 12) {            // 1x1 with the weight fragments read from global memory (explicit request only; w_frag with one tap)
-        if (!(bf3 && vec_out && conv_pw_frag_supports(d, splits))) return GA_E_UNSUPPORTED;
-        rc = conv_pw_frag_dispatch(k, stream, vec_out);
-    } else if (tile == 9) {             // quadrant tile: 3x3 on 4 x 4 images without the products of the zero frame (explicit request only; w_frag in the tile-8 order)
-        if (!(bf3 && vec_out && conv_quad3_supports(d, splits))) return GA_E_UNSUPPORTED;
-        rc = conv_quad3_dispatch(k, stream, vec_out, splits);
-    } else if (tile >= 5 && tile <= 8) { // halo-staged 3x3 (explicit request only: the tune table names it per shape)
-        if (!(bf3 && vec_out && conv_halo3_supports(d))) return GA_E_UNSUPPORTED;
-        rc = conv_halo3_dispatch(k, stream, tile, vec_out, splits);
-    } else if (bf3) {
-        rc = conv_bf3_dispatch(k, stream, tile, vec_out, splits);
-    } else {
-        switch (tile) {
-            case 1: rc = launch_conv<2, 2, 2, 2>(k, stream, vec, vec_out, splits); break;
-            case 2: rc = launch_conv<4, 1, 1, 2>(k, stream, vec, vec_out, splits); break;
-            case 3: rc = launch_conv<2, 2, 1, 1>(k, stream, vec, vec_out, splits); break;
-            case 4: rc = launch_conv<4, 1, 1, 1>(k, stream, vec, vec_out, splits); break;
-            default: return GA_E_UNSUPPORTED;
-        }
-    }
-    if (rc != GA_OK || splits == 1) return rc;
-    long items = M * d.Cout / (vec_out ? 4 : 1);
-    long blocks = (items + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, k, (int)M, splits, vec_out);
-    return check_launch();
-}

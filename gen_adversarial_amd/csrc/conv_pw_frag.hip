@@ -17,6 +17,7 @@
 // results are bitwise those of tiles 1 - 4.  No split-K, one source, pixel counts that are multiples of 128.
 #include "conv_split.h"
 #include "conv_epilogue.h"
+#include "conv_families.h"
 
 namespace ga {
 
@@ -194,32 +195,28 @@ static void launch_pw_frag_inst(const ga_conv_desc& d, hipStream_t stream, dim3 
     X(0x11, 1, GA_ACT_SILU)  \
     X(0x20, 2, GA_ACT_NONE)
 
-// 1 when tile code 12 takes the descriptor: 1x1 / stride 1 / pad 0, one source whose channel count is a multiple of the MFMA k step,
-// whole 128-pixel tiles, no split-K, the fragment-ordered weight copy aligned when given, a prologue the decoder / encoder 1x1 layers use (a per-row
-// affine needs the 16 pixels a staging thread converts to lie in one image)
-int conv_pw_frag_supports(const ga_conv_desc& d, const int splits) {
-    if (d.KH != 1 || d.KW != 1 || d.sn != 1 || d.sd != 1 || d.pad != 0 || d.C2 != 0) return 0;
-    if (d.Ho != d.Hi || d.Wo != d.Wi || d.C1 % 16 != 0 || splits != 1) return 0;
-    if (((long)d.N * d.Ho * d.Wo) % 128 != 0) return 0;
-    if (d.w_frag && !aligned16(d.w_frag)) return 0;
+// GA_OK when tile code 12 takes the descriptor: the split-bf16 operands and vector output, 1x1 / stride 1 / pad 0, one source whose
+// channel count is a multiple of the MFMA k step, whole 128-pixel tiles, no split-K, the fragment-ordered weight copy aligned when
+// given, a prologue the decoder / encoder 1x1 layers use (a per-row affine needs the 16 pixels a staging thread converts to lie in
+// one image)
+int conv_pw_frag_check(const ga_conv_desc& d, const conv_req& r) {
+    if (!(r.bf3 && r.vec_out)) return GA_E_UNSUPPORTED;
+    if (d.KH != 1 || d.KW != 1 || d.sn != 1 || d.sd != 1 || d.pad != 0 || d.C2 != 0) return GA_E_UNSUPPORTED;
+    if (d.Ho != d.Hi || d.Wo != d.Wi || d.C1 % 16 != 0 || r.splits != 1) return GA_E_UNSUPPORTED;
+    if (((long)d.N * d.Ho * d.Wo) % 128 != 0) return GA_E_UNSUPPORTED;
+    if (d.w_frag && !aligned16(d.w_frag)) return GA_E_UNSUPPORTED;
     const int mode = conv_pro_mode(d);
     switch (mode) {
-        GA_PWF_MODES(GA_MODE_CASE) return mode != 0x20 || (d.Ho * d.Wo) % PSL == 0;
-        default: return 0;
+        GA_PWF_MODES(GA_MODE_CASE) return mode != 0x20 || (d.Ho * d.Wo) % PSL == 0 ? GA_OK : GA_E_UNSUPPORTED;
+        default: return GA_E_UNSUPPORTED;
     }
 }
 
-// tile code 12 of ga_conv_desc.tile; called by ga_conv2d after validation (split-bf16 operands, vector output, supports())
-int conv_pw_frag_dispatch(const ga_conv_desc& d, hipStream_t stream, int vec_out) {
+int conv_pw_frag_launch(const ga_conv_desc& d, const conv_req& r, hipStream_t stream) {
     constexpr int BM = 128, BN = 128;
-    const int M = d.N * d.Ho * d.Wo;
     const int nk32 = (d.C1 + 31) / 32;
-    const int tilesM = M / BM, tilesN = (d.Cout + BN - 1) / BN;
-    size_t lds = (size_t)2 * BM * PLD * 2;
-    const size_t lds_c = (size_t)BM * (BN + 4) * sizeof(float);
-    if (lds_c > lds) lds = lds_c;
-    const dim3 grid(tilesM * tilesN, 1);
-#define GA_PWF(MODE, A, C) case MODE: launch_pw_frag_inst<A, C>(d, stream, grid, lds, tilesN, M, nk32, vec_out); break;
+    const conv_tiling t = conv_tile_grid(d, BM, BN, 1, (size_t)2 * BM * PLD * 2);      // (whole tiles only: tilesM = M / 128)
+#define GA_PWF(MODE, A, C) case MODE: launch_pw_frag_inst<A, C>(d, stream, t.grid, t.lds, t.tilesN, t.M, nk32, r.vec_out); break;
     switch (conv_pro_mode(d)) {
 #ifdef GA_PWF_EXP_ONLY
         GA_PWF_MODES_EXP(GA_PWF)

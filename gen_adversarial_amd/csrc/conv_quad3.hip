@@ -30,10 +30,9 @@
 #include <utility>
 #include "conv_split.h"
 #include "conv_epilogue.h"
+#include "conv_families.h"
 
 namespace ga {
-
-int conv_halo3_supports(const ga_conv_desc& d);             // conv_halo3.hip
 
 namespace {
 
@@ -255,30 +254,26 @@ void launch_quad_inst(const ga_conv_desc& d, hipStream_t stream, dim3 grid, size
 
 }  // namespace
 
-// 1 when ga_conv2d takes d on tile 9: what the halo kernels take (3x3 / stride 1 / pad 1, one source of C1 % 32 == 0 channels, an
-// instantiated prologue), 4 x 4 images in whole groups of 32 (or one partial group: N < 32), the fragment-ordered weights, split-K
-// over whole chunks
-int conv_quad3_supports(const ga_conv_desc& d, const int splits) {
-    if (!conv_halo3_supports(d) || d.Hi != 4 || d.Wi != 4 || (d.N % 32 != 0 && d.N > 32)) return 0;
-    return d.w_frag && aligned16(d.w_frag) && splits <= d.C1 / QK;
+// GA_OK when ga_conv2d takes d on tile 9: the split-bf16 operands and vector output, what the halo kernels take (3x3 / stride 1 /
+// pad 1, one source of C1 % 32 == 0 channels, an instantiated prologue), 4 x 4 images in whole groups of 32 (or one partial group:
+// N < 32), the fragment-ordered weights of tile 8, split-K over whole chunks
+int conv_quad3_check(const ga_conv_desc& d, const conv_req& r) {
+    if (!(r.bf3 && r.vec_out && conv_halo3_shape_ok(d)) || d.Hi != 4 || d.Wi != 4 || (d.N % 32 != 0 && d.N > 32)) return GA_E_UNSUPPORTED;
+    return d.w_frag && aligned16(d.w_frag) && r.splits <= d.C1 / QK ? GA_OK : GA_E_UNSUPPORTED;
 }
 
-int conv_quad3_dispatch(const ga_conv_desc& d, hipStream_t stream, int vec_out, int splits) {
-    constexpr int BM = 128, BN = 128;     // (tilesM = N * 16 / 128 for whole groups: tile 8's count)
-    if (!vec_out) return GA_E_UNSUPPORTED;
-    const int M = d.N * 16, nkc = d.C1 / QK;
-    const int tilesM = 4 * ((d.N + 31) / 32), tilesN = (d.Cout + BN - 1) / BN;
-    const size_t lds = 2 * QBUF;                             // two patch buffers; the epilogue's [128][132] floats fit in them
+int conv_quad3_launch(const ga_conv_desc& d, const conv_req& r, hipStream_t stream) {
+    constexpr int BM = 128, BN = 128;
+    const int nkc = d.C1 / QK;
+    // two patch buffers; the epilogue's [128][132] floats fit in them
     static_assert(2 * QBUF >= BM * (BN + 4) * sizeof(float) && 2 * QBUF <= 80 * 1024, "two workgroups per CU");
-    const dim3 grid(tilesM * tilesN, splits);
+    conv_tiling t = conv_tile_grid(d, BM, BN, r.splits, 2 * QBUF);
+    t.tilesM = 4 * ((d.N + 31) / 32);       // four quadrant tiles per group of 32 images, a partial group included (= N * 16 / 128
+    t.grid.x = t.tilesM * t.tilesN;         // for whole groups: tile 8's count)
 #define GA_QUAD(MODE, A, C, WIDE) \
-    case MODE: launch_quad_inst<A, C>(d, stream, grid, lds, tilesN, M, nkc); break;
+    case MODE: launch_quad_inst<A, C>(d, stream, t.grid, t.lds, t.tilesN, t.M, nkc); break;
     switch (conv_pro_mode(d)) {
-#ifdef GA_HALO_EXP_ONLY     // quick experiment builds (make hexp): two prologues only
-        GA_CONV3_MODES_EXP(GA_QUAD)
-#else
         GA_CONV3_MODES(GA_QUAD)
-#endif
         default: return GA_E_UNSUPPORTED;
     }
 #undef GA_QUAD

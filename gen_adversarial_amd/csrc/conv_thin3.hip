@@ -18,6 +18,7 @@
 // 55 KB window: ONE workgroup per CU; the next window's 12 loads per thread are in flight under the MFMAs and the epilogue.
 #include "conv_split.h"
 #include "conv_epilogue.h"
+#include "conv_families.h"
 
 namespace ga {
 
@@ -170,11 +171,14 @@ static void launch_thin_inst(const ga_conv_desc& d, hipStream_t stream, dim3 gri
     hipLaunchKernelGGL((conv_thin3_kernel<CIN, AFF, ACT>), grid, dim3(256), lds, stream, d, g, M);
 }
 
-// 1 when tile code 11 takes the descriptor: 3x3 / stride 1 / pad 1, one source of exactly 32 or 64 channels, images of 8 x 16 tiles
-int conv_thin3_supports(const ga_conv_desc& d) {
-    if (d.KH != 3 || d.KW != 3 || d.sn != 1 || d.sd != 1 || d.pad != 1 || d.C2 != 0 || (d.C1 != 32 && d.C1 != 64)) return 0;
-    if (d.Ho != d.Hi || d.Wo != d.Wi || d.Ho % TK_TH || d.Wo % TK_TW || d.Wo > 255 * TK_TW) return 0;
-    return conv3_mode_supported(d);
+// GA_OK when tile code 11 takes the descriptor: the split-bf16 operands and vector output, no split-K, d.w_frag in the thin order
+// (WeightStore.frag_thin: [Cout tile of 32][tap][k step][hi | lo][lane][8], C1 / 16 k steps per tap), 3x3 / stride 1 / pad 1, one
+// source of exactly 32 or 64 channels, images of 8 x 16 tiles, a prologue of GA_CONV3_MODES
+int conv_thin3_check(const ga_conv_desc& d, const conv_req& r) {
+    if (!(r.bf3 && r.vec_out) || r.splits != 1 || !d.w_frag || !aligned16(d.w_frag)) return GA_E_UNSUPPORTED;
+    if (d.KH != 3 || d.KW != 3 || d.sn != 1 || d.sd != 1 || d.pad != 1 || d.C2 != 0 || (d.C1 != 32 && d.C1 != 64)) return GA_E_UNSUPPORTED;
+    if (d.Ho != d.Hi || d.Wo != d.Wi || d.Ho % TK_TH || d.Wo % TK_TW || d.Wo > 255 * TK_TW) return GA_E_UNSUPPORTED;
+    return conv3_mode_supported(d) ? GA_OK : GA_E_UNSUPPORTED;
 }
 
 template <int CIN>
@@ -188,10 +192,8 @@ static int thin_dispatch_c(const ga_conv_desc& d, hipStream_t stream, dim3 grid,
     return check_launch();
 }
 
-// called by ga_conv2d after validation (tile 11; vec_out and the split-bf16 operands checked there); needs d.w_frag in the thin order
-// (WeightStore.frag_thin: [Cout tile of 32][tap][k step][hi | lo][lane][8], C1 / 16 k steps per tap)
-int conv_thin3_dispatch(const ga_conv_desc& d, hipStream_t stream, int vec_out, int splits) {
-    if (!vec_out || splits != 1 || !d.w_frag || !aligned16(d.w_frag) || !conv_thin3_supports(d)) return GA_E_UNSUPPORTED;
+// a persistent grid of its own (runs of 2-D tiles per workgroup, grid.y = 32-channel output tiles), not conv_tile_grid's
+int conv_thin3_launch(const ga_conv_desc& d, const conv_req&, hipStream_t stream) {
     const int M = d.N * d.Ho * d.Wo;
     thin_geom g;
     g.H = d.Ho; g.W = d.Wo;

@@ -37,10 +37,12 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
-# ---- which explicit tile codes ga_conv2d takes for a descriptor (GA_E_UNSUPPORTED otherwise).  A restatement of the checks in
-#      csrc/conv_mfma.hip (ga_conv2d: the split-bf16 and vector-output preconditions), csrc/conv_bf3.hip (conv_bf3_supports),
-#      csrc/conv_halo3.hip (conv_halo3_supports, halo_geometry, launch_halo, launch_halo_bd), csrc/conv_quad3.hip (conv_quad3_supports), csrc/conv_thin3.hip
-#      (conv_thin3_supports) and csrc/conv_pw_frag.hip (conv_pw_frag_supports); tests/test_plan_convs_gpu.py checks that the library refuses exactly what these reject.
+# ---- which explicit tile codes ga_conv2d takes for a descriptor (GA_E_UNSUPPORTED otherwise).  Each *_ok predicate restates ONE
+#      function of the library, the conv_<family>_check declared in csrc/conv_families.h: halo_ok and frag_ok conv_halo3_check
+#      (csrc/conv_halo3.hip, tiles 5 - 7 and tile 8), quad_ok conv_quad3_check (csrc/conv_quad3.hip), thin_ok conv_thin3_check
+#      (csrc/conv_thin3.hip), pw_ok conv_pw_frag_check (csrc/conv_pw_frag.hip).  What a check is told (conv_req: vec_out, bf3, the
+#      clamped splits) comes from operand_classes and split_factor in csrc/conv2d.hip: _bf3_vec_out and _splits here.
+#      tests/test_plan_convs_gpu.py checks that the library refuses exactly what these reject.
 _HALO_HK, _HALO_LDH = 32, 40                # conv_halo3.hip: channels per chunk, bf16 per LDS pixel row
 _BF3_MODES = (0x000, 0x100, 0x001, 0x002, 0x003, 0x004, 0x010, 0x011, 0x020, 0x021)
 _HALO_MODES = (0x00, 0x01, 0x02, 0x03, 0x04, 0x10, 0x11, 0x20)
@@ -62,7 +64,8 @@ def _splits(d, splits=None) -> int:
 
 
 def _bf3_vec_out(d, splits: int) -> bool:
-    """the split-bf16 operands are usable (ga_conv2d's `bf3`) and the output is written as float4 (`vec_out`)"""
+    """conv_req.bf3 and conv_req.vec_out (operand_classes, csrc/conv2d.hip): the split-bf16 operands are usable, with a prologue
+    conv_bf3_mode_ok has a kernel for, and the output is written as float4"""
     c2 = d.C2 > 0
     vec = d.C1 % 4 == 0 and d.C2 % 4 == 0 and d.ldx % 4 == 0 and (not c2 or d.ldx2 % 4 == 0) and _a16(d.x) and _a16(d.w) \
         and (not c2 or _a16(d.x2)) and (not d.pro_scale or (_a16(d.pro_scale) and _a16(d.pro_shift)))
@@ -76,7 +79,7 @@ def _bf3_vec_out(d, splits: int) -> bool:
 
 
 def _halo_3x3(d) -> bool:
-    """conv_halo3_supports: 3x3 / stride 1 / pad 1, one source of C1 % 32 == 0 channels, 128-pixel tiles of whole rows (or whole
+    """conv_halo3_shape_ok: 3x3 / stride 1 / pad 1, one source of C1 % 32 == 0 channels, 128-pixel tiles of whole rows (or whole
     small images) or 128-pixel segments of one row"""
     if (d.KH, d.KW, d.sn, d.sd, d.pad, d.C2) != (3, 3, 1, 1, 1, 0) or d.Ho != d.Hi or d.Wo != d.Wi or d.C1 % _HALO_HK:
         return False
@@ -86,7 +89,7 @@ def _halo_3x3(d) -> bool:
 
 
 def _halo_geometry(d, bm: int = 128, ldh: int = _HALO_LDH):
-    """halo_geometry: (NI images per tile, P patch pixels, IS bf16 per image patch)"""
+    """halo_geometry, as halo_plan_for uses it (csrc/conv_halo3.hip): (NI images per tile, P patch pixels, IS bf16 per image patch)"""
     howo = d.Ho * d.Wo
     wide = d.Wo >= bm
     tw = bm if wide else d.Wo
@@ -102,7 +105,8 @@ def _halo_geometry(d, bm: int = 128, ldh: int = _HALO_LDH):
 
 
 def halo_ok(d, tile: Optional[int] = None, splits: Optional[int] = None) -> bool:
-    """ga_conv2d runs d on the LDS-staged halo kernel, tile 5 (128 x 128), 6 (128 x 64) or 7 (128 x 32; default d.tile)"""
+    """conv_halo3_check for tile 5 (128 x 128), 6 (128 x 64) or 7 (128 x 32; default d.tile): ga_conv2d runs d on the LDS-staged halo
+    kernel (halo_plan_for's tile 5 - 7 branch: patch slots, the WIDE prologues, split-K over chunks, 160 KB of LDS)"""
     tile = d.tile if tile is None else tile
     s = _splits(d, splits)
     if tile not in (5, 6, 7) or not _bf3_vec_out(d, s) or not _halo_3x3(d):
@@ -115,7 +119,8 @@ def halo_ok(d, tile: Optional[int] = None, splits: Optional[int] = None) -> bool
 
 
 def frag_ok(d, splits: Optional[int] = None) -> bool:
-    """ga_conv2d runs d on tile 8: the halo kernel with its weight fragments read from d.w_frag"""
+    """conv_halo3_check for tile 8: ga_conv2d runs d on the halo kernel with its weight fragments read from d.w_frag
+    (halo_plan_for's tile 8 branch: patch, slot and prologue tables within 80 KB of LDS)"""
     s = _splits(d, splits)
     if not d.w_frag or not _a16(d.w_frag) or not _bf3_vec_out(d, s) or not _halo_3x3(d):
         return False
@@ -132,7 +137,7 @@ def frag_ok(d, splits: Optional[int] = None) -> bool:
 
 
 def quad_ok(d, splits: Optional[int] = None) -> bool:
-    """ga_conv2d runs d on tile 9 (conv_quad3_supports): what the halo kernels take, on 4 x 4 images in whole groups of 32, with tile
+    """conv_quad3_check: ga_conv2d runs d on tile 9, what the halo kernels take, on 4 x 4 images in whole groups of 32, with tile
     8's d.w_frag (a batch of fewer than 32 images runs as one partial group).  (Tile 8's LDS bound does not apply: the kernel keeps two 36-KB patch buffers and no tables at any channel count.)"""
     s = _splits(d, splits)
     if not d.w_frag or not _a16(d.w_frag) or not _bf3_vec_out(d, s) or not _halo_3x3(d):
@@ -141,7 +146,7 @@ def quad_ok(d, splits: Optional[int] = None) -> bool:
 
 
 def thin_ok(d, splits: Optional[int] = None) -> bool:
-    """ga_conv2d runs d on tile 11: the persistent weights-resident 3x3 kernel of 32 or 64 input channels (d.w_frag in its order)"""
+    """conv_thin3_check: ga_conv2d runs d on tile 11, the persistent weights-resident 3x3 kernel of 32 or 64 input channels (d.w_frag in its order)"""
     s = _splits(d, splits)
     if s != 1 or not d.w_frag or not _a16(d.w_frag) or not _bf3_vec_out(d, s):
         return False
@@ -151,7 +156,7 @@ def thin_ok(d, splits: Optional[int] = None) -> bool:
 
 
 def pw_ok(d, splits: Optional[int] = None) -> bool:
-    """ga_conv2d runs d on tile 12 (conv_pw_frag_supports): the 1x1 kernel with its weight fragments read from d.w_frag (one tap;
+    """conv_pw_frag_check: ga_conv2d runs d on tile 12, the 1x1 kernel with its weight fragments read from d.w_frag (one tap;
     without the copy the kernel gathers them from w_hi / w_lo, slower: the engine always builds it, Engine._want)"""
     s = _splits(d, splits)
     if s != 1 or not _a16(d.w_frag) or not _bf3_vec_out(d, s):
