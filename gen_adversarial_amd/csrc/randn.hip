@@ -3,12 +3,11 @@
 // `draw` under `seed` depends on (seed, draw, tensor, R, e) alone, never on the launch geometry.
 // Store-bound: one thread per quad = one Philox call, four normals, one 16-byte store.
 #include "ga_common.h"
+#include "philox.h"
 
 using namespace ga;
 
 namespace {
-
-constexpr unsigned PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u, PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
 
 struct randn_args {
     float* y; long rows; unsigned long quads;      // quads per row (inner / 4)
@@ -16,22 +15,7 @@ struct randn_args {
     float scale; int mode;
 };
 
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&x)[4]) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const unsigned hi0 = __umulhi(PHILOX_M0, c0), lo0 = PHILOX_M0 * c0;
-        const unsigned hi1 = __umulhi(PHILOX_M1, c2), lo1 = PHILOX_M1 * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += PHILOX_W0; k1 += PHILOX_W1;
-    }
-    x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
-}
-
-// u = ((x >> 9) + 0.5) * 2^-23: the sum needs 24 bits, so every step is exact; 2^-24 <= u <= 1 - 2^-24
-__device__ __forceinline__ float uniform01(unsigned x) { return ((float)(x >> 9) + 0.5f) * 1.1920928955078125e-07f; }
-
-// quad q of row r: the four values of y[r, 4q .. 4q+3].  logf / sqrtf / sincospif are the library's accurate forms (the fast
-// v_log_f32 path loses 1e-6 relative near u = 1, where ln u is tiny): the kernel waits on its stores either way.
+// quad q of row r: the four values of y[r, 4q .. 4q+3] (the generator itself: philox.h)
 __device__ __forceinline__ floatx4 randn_quad(const randn_args& a, const unsigned long r, const unsigned long q) {
     unsigned x[4];
     philox4x32_10((unsigned)q, (unsigned)(a.row0 + r), a.stream, a.draw, a.k0, a.k1, x);
@@ -40,14 +24,9 @@ __device__ __forceinline__ floatx4 randn_quad(const randn_args& a, const unsigne
         v[0] = __uint_as_float(x[0]); v[1] = __uint_as_float(x[1]); v[2] = __uint_as_float(x[2]); v[3] = __uint_as_float(x[3]);
         return v;
     }
+    v = box_muller_quad(x);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const float rad = sqrtf(-2.0f * logf(uniform01(x[2 * j])));
-        float sn, cs;
-        sincospif(2.0f * uniform01(x[2 * j + 1]), &sn, &cs);
-        v[2 * j] = a.scale * (rad * cs);
-        v[2 * j + 1] = a.scale * (rad * sn);
-    }
+    for (int j = 0; j < 4; ++j) v[j] = a.scale * v[j];
     return v;
 }
 

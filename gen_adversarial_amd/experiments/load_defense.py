@@ -6,7 +6,7 @@ Config / factory layer with the reference's surface (src/experiments/load_defens
 
 Built: every defense_type of the reference for every experiment — 'base' | 'trades' (classifier only), 'ablation' (noise /
 blur), 'ours' (ids: NVAE; gender: e4e + StyleGAN2; cars: Style-Transformer + StyleGAN2) and the competitors 'A-VAE' / 'ND-VAE'
-(load_defense.py:95-124) — plus the reference's attack sets (DeepFool, C&W, AutoAttack) and `args.pgd` (PGD-Linf).
+(load_defense.py:95-124) — plus the reference's attack sets (DeepFool, C&W, AutoAttack) `args.pgd` (PGD-Linf) and `args.nes` (NES, black-box).
 An unknown experiment or defense type raises NotImplementedError, like in the reference (:75,:144).
 """
 from argparse import Namespace
@@ -14,6 +14,7 @@ from argparse import Namespace
 import yaml
 
 from ..attacks.l2_attacks import AutoAttack, CW, DeepFool
+from ..attacks.nes import NESAttack
 from ..attacks.pgd import PGDLinf
 from ..defenses.ablations.models import GaussianBlurDefenseModel, GaussianNoiseDefenseModel
 from ..defenses.competitors.a_vae import AVaeDefenseModel, load_AVAE
@@ -65,6 +66,12 @@ def load(args: Namespace):
         hl_instance = TransStyleGanDefenseModel
     else:
         raise NotImplementedError
+    # NES, the score-based black-box attack (attacks/nes.py; not in the reference tree), at PGD's setting; selected with `--attack nes` of
+    # experiments.seeded_defense (that driver's own choice: its queries are seeded by dataset index there).
+    # 2 * pairs query rows per image and step; a query call holds what 1024 rows of 64 x 64 images hold (8 images at 'ids').
+    nes_pairs = 64
+    args.nes = NESAttack(norm='Linf', eps=8.0 / 255.0, step_size=2.0 / 255.0, steps=40, pairs=nes_pairs, sigma=1e-3,
+                         query_images=max(1, (1024 * 64 * 64) // (args.image_size ** 2 * 2 * nes_pairs)))
 
     if args.defense_type in ('base', 'trades'):
         defense_model = base_classifier

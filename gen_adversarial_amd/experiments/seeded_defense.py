@@ -11,7 +11,10 @@ draws at its own rows (one ga_randn per image), so the static r::W shards, whose
 draws as any other partition — as long as the attack keeps all images of the batch in its calls (an attack that drops finished
 images from a call shifts the others' rows).  The reference's one-image attacks then run image by image, each from draw 0.
 The draw number of a call counts the calls since the restart, so results are comparable between runs with the same --batch_images.
-Everything else — the torch seeds of the attacks' own starting points included — is test_defense's.
+Everything else — the torch seeds of the attacks' own starting points included — is test_defense's, except for NES (--attack nes):
+its directions and its starting point come from the same generator at rows (index of the image in the dataset) x pairs
+(`NESAttack.image_index`), so an image's queries are the same in every partition; the defender's own draws under its query calls
+count rows from the batch's first image.
 """
 from __future__ import annotations
 
@@ -27,6 +30,10 @@ import torch
 import torch.distributed as dist
 
 from . import test_defense as drv
+
+
+OWN_ATTACKS = ('nes',)                                 # --attack choices of this driver beside test_defense's
+RESULT_KEYS = {**drv.RESULT_KEYS, 'nes': 'NES'}        # results.json column of each attack
 
 
 def noise_owner(defense_model):
@@ -46,7 +53,8 @@ def evaluate_seeded(defense_model, attacks: Dict[str, Callable], images: torch.T
     names = list(attacks)
     n, bi = images.shape[0], max(1, int(batch_images))
     out = torch.zeros(n, 1 + len(names))
-    batched = {k: a for k, a in attacks.items() if bi == 1 or getattr(a, 'batched', False)}
+    indexed = {k: a for k, a in attacks.items() if hasattr(a, 'image_index')}      # NES: see below
+    batched = {k: a for k, a in attacks.items() if k not in indexed and (bi == 1 or getattr(a, 'batched', False))}
     try:
         for lo in range(0, n, bi):
             hi = min(n, lo + bi)
@@ -55,10 +63,19 @@ def evaluate_seeded(defense_model, attacks: Dict[str, Callable], images: torch.T
             out[lo:hi, 0] = t[:, 0]
             for j, k in enumerate(batched):
                 out[lo:hi, 1 + names.index(k)] = t[:, 1 + j]
-            for i in range(lo, hi) if len(batched) < len(names) else ():
+            # attacks with an `image_index` (NES) draw their own numbers by dataset index, and their calls hold query rows, not the
+            # batch's images: the defender's rows then count from the batch's first image, one draw per call from 0
+            for k, a in indexed.items():
+                owner.seeded_noise(int(seed), draw=0, first_row=int(index_of(lo)) * eot)
+                a.image_index = torch.tensor([int(index_of(i)) for i in range(lo, hi)])
+                success, bound, _ = a(images[lo:hi].clamp(0.0, 1.0), labels[lo:hi], defense_model)
+                success = torch.as_tensor(success).view(-1).cpu()
+                bound = torch.as_tensor(bound, dtype=torch.float32).view(-1).cpu()
+                out[lo:hi, 1 + names.index(k)] = torch.where(success, bound, torch.full_like(bound, drv.FAILED))
+            for i in range(lo, hi) if len(batched) + len(indexed) < len(names) else ():
                 owner.seeded_noise(int(seed), draw=0, first_row=int(index_of(i)) * eot)
                 for k in names:
-                    if k not in batched:
+                    if k not in batched and k not in indexed:
                         success, bound, _ = attacks[k](images[i:i + 1].clamp(0.0, 1.0), labels[i:i + 1], defense_model)
                         out[i, 1 + names.index(k)] = float(bound) if success else drv.FAILED
     finally:
@@ -99,7 +116,7 @@ def run_worker(rank: int, world: int, args, make_model: Callable, dataset: Tuple
         table = drv.gather_results(local, world, dev)
     res = None
     if rank == 0:
-        cols = {drv.RESULT_KEYS.get(name, name): table[:, 1 + j].tolist() for j, name in enumerate(attacks.keys())}
+        cols = {RESULT_KEYS.get(name, name): table[:, 1 + j].tolist() for j, name in enumerate(attacks.keys())}
         res = drv.merge_results(results_path or os.path.join(args.results_folder, 'results.json'), float(table[:, 0].mean().item()), cols)
     if world > 1:
         dist.barrier()
@@ -107,12 +124,18 @@ def run_worker(rank: int, world: int, args, make_model: Callable, dataset: Tuple
 
 
 def parse_args(argv=None):
+    """test_defense's flags + --noise_seed; `--attack nes` is this driver's own choice and never reaches test_defense's parser"""
     argv = sys.argv[1:] if argv is None else list(argv)
     p = argparse.ArgumentParser(add_help=False)
     p.add_argument('--noise_seed', type=int, required=True, help='seed of the defender\'s draws (ga_randn)')
+    p.add_argument('--attack', type=str, default=None, help='test_defense\'s choices, or nes (black-box, attacks/nes.py)')
     own, rest = p.parse_known_args(argv)
+    if own.attack is not None and own.attack not in OWN_ATTACKS:
+        rest += ['--attack', own.attack]
     args = drv.parse_args(rest)
     args.noise_seed = own.noise_seed
+    if own.attack in OWN_ATTACKS:
+        args.attack = own.attack
     return args
 
 
@@ -130,6 +153,8 @@ def main():
             a.attacks = {'pgd': a.pgd}
         elif a.attack == 'pgd-bpda':
             a.attacks = {'pgd-bpda': getattr(a, 'pgd_bpda', None) or type(a.pgd)(eps=a.pgd.eps, step_size=a.pgd.step_size, steps=a.pgd.steps, bpda=True)}
+        elif a.attack == 'nes':
+            a.attacks = {'nes': a.nes}
         elif a.attack is not None:
             a.attacks = {k: v for k, v in a.attacks.items() if k == a.attack}
         return a, m

@@ -643,6 +643,34 @@ int ga_randn(float* y, long rows, long inner, unsigned long seed, unsigned draw,
              int mode, float* coef, float coef_eps, float* ws, long ws_floats, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * ga_nes_perturb / ga_nes_grad — the device halves of the NES black-box attack (Ilyas et al. 2018;
+ * gen_adversarial_amd/attacks/nes.py): antithetic Gaussian queries x +- sigma * u_i around every image, and the gradient estimate
+ * sum_i c_i u_i from their loss differences.  The directions are never stored: both kernels regenerate them from ga_randn's
+ * generator, so a query is a pure function of (seed, draw, row, element) that gen_adversarial_amd/attacks/nes_ref.py restates in
+ * numpy, whatever the batch, the chunking or the rank.  Not plan ops: called directly, scalars like ga_randn.
+ *
+ * The contract: the direction of sample i of image b is
+ *     z(b, i, e) = the ga_randn normal (scale 1, above) of (seed, draw, tensor, row = image_row[b] + i, element e),
+ * image_row being a DEVICE array of `images` unsigned first rows, or NULL, which means image_row[b] = row0 + b * pairs.
+ * (Counter word 1 is (unsigned)(image_row[b] + i): with an array, the caller owes image_row[b] + pairs <= 2^32.)
+ *
+ * ga_nes_perturb:  x [images, inner] (NCHW images flattened, inner = 3 H W), y [images * pairs * 2, inner], written:
+ *     y[(b * pairs + i) * 2 + s, e] = clamp(x[b, e] + (s ? -sigma : +sigma) * z(b, i, e), lo, hi);   lo > hi: no clamp.
+ *   One thread per quad computes z once and writes both signs with 16-byte stores.
+ * ga_nes_grad:  c [images * pairs] (the loss differences), g [images, inner], written:
+ *     g[b, e] = scale * sum_{i = 0 .. pairs-1} c[b * pairs + i] * z(b, i, e),
+ *   accumulated in fp32 in index order i = 0, 1, ... by one thread per (image, quad), no atomics: the same bits every run, and the
+ *   same bits for an image alone or in a batch.
+ * GA_E_BADARG: a NULL x, y, c or g; images, inner or pairs <= 0; a row past 2^32 (image_row NULL: row0 + images * pairs > 2^32);
+ * GA_E_UNSUPPORTED: inner % 4 != 0 (ga_nes_grad: more than 65535 images);  GA_E_ALIGN: x, y or g not 16-byte aligned.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define GA_RANDN_STREAM_NES 2147483649     /* counter word 2 of the attack's directions: no defender tensor draws there */
+int ga_nes_perturb(const float* x, float* y, long images, long inner, long pairs, unsigned long seed, unsigned draw, unsigned tensor,
+                   unsigned long row0, const unsigned* image_row, float sigma, float lo, float hi, void* stream);
+int ga_nes_grad(const float* c, float* g, long images, long inner, long pairs, unsigned long seed, unsigned draw, unsigned tensor,
+                unsigned long row0, const unsigned* image_row, float scale, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Plans: a forward or backward pass is a flat list of the ops above, built once on the host and replayed by ONE call.
  * ------------------------------------------------------------------------------------------------------------------ */
 typedef struct ga_axpby_desc { const float* x; float* y; long n; float alpha, beta; } ga_axpby_desc;
@@ -726,6 +754,8 @@ const char* ga_last_hip_error(void);
  * a formerly refused or unused mode value changes no layout and no existing call, so the version stays.) */
 /* (ga_randn is an entry point of its own beside the plan: no descriptor and not ga_op changes, and the binding
  * looks every declared symbol up when it loads, so a library built before ga_randn existed is refused by name: the version stays.) */
+/* (ga_nes_perturb and ga_nes_grad likewise: entry points of their own with scalar arguments, no descriptor, ga_op untouched, and a
+ * library without them is refused by name when the binding looks them up: the version stays.) */
 #define GA_ABI_VERSION 8
 int ga_abi_version(void);
 unsigned long ga_sizeof_op(void);
