@@ -408,14 +408,23 @@ class FABAttack(UntargetedL2Attack):
 # ---------------------------------------------------------------------------------------------------------------------
 class AutoAttack(UntargetedL2Attack):
     """APGD-CE at bounds .5/1/4, APGD-DLR at .5/2/4 (when > 3 classes), FAB; smallest successful distortion wins.  Batched:
-    an image leaves an escalation as soon as one bound succeeds for it, the remaining images go on as a smaller batch."""
+    an image leaves an escalation as soon as one bound succeeds for it, the remaining images go on as a smaller batch.
+    `with_square=True` adds the fourth member of AutoAttack's standard set, which the reference leaves out ("Square Attack is not
+    tested"): after FAB, Square Attack (L2, attacks/square.py) escalates over the CE bounds .5/1/4 with `square_queries` queries
+    each.  Its stage draws by position in its own call (image b of a call at generator row b), so unlike SquareAttack with an
+    `image_index` an image's proposals there depend on which images are still attacked.  The default runs exactly the three
+    stages above."""
     batched = True
 
-    def __init__(self):
+    def __init__(self, with_square: bool = False, square_queries: int = 5000, square_seed: int = 0):
         mk = lambda bound, ce: APGDAttack(n_iter=64, rho=0.75, max_bound=bound, ce_loss=ce)   # noqa: E731
         self.ce = [mk(0.5, True), mk(1.0, True), mk(4.0, True)]
         self.dlr = [mk(0.5, False), mk(2.0, False), mk(4.0, False)]
         self.fab = FABAttack(n_iter=128, alpha_max=0.1, eta=1.05, beta=0.9)
+        self.square = []
+        if with_square:
+            from .square import SquareAttack
+            self.square = [SquareAttack(norm='L2', eps=a.max_bound, n_queries=square_queries, seed=square_seed) for a in self.ce]
 
     @staticmethod
     def _tensors(res, image):
@@ -455,4 +464,6 @@ class AutoAttack(UntargetedL2Attack):
         if n_classes > 3:
             best = self._better(best, self._escalate(self.dlr, image, gt_label, net))
         best = self._better(best, self._tensors(self.fab(image, gt_label, net), image))
+        if self.square:
+            best = self._better(best, self._escalate(self.square, image.clamp(0.0, 1.0), gt_label, net))
         return _ret(*best)

@@ -6,7 +6,7 @@ Config / factory layer with the reference's surface (src/experiments/load_defens
 
 Built: every defense_type of the reference for every experiment — 'base' | 'trades' (classifier only), 'ablation' (noise /
 blur), 'ours' (ids: NVAE; gender: e4e + StyleGAN2; cars: Style-Transformer + StyleGAN2) and the competitors 'A-VAE' / 'ND-VAE'
-(load_defense.py:95-124) — plus the reference's attack sets (DeepFool, C&W, AutoAttack) `args.pgd` (PGD-Linf) and `args.nes` (NES, black-box).
+(load_defense.py:95-124) — plus the reference's attack sets (DeepFool, C&W, AutoAttack) `args.pgd` (PGD-Linf), `args.nes` (NES, black-box) and `args.square` (Square Attack, black-box).
 An unknown experiment or defense type raises NotImplementedError, like in the reference (:75,:144).
 """
 from argparse import Namespace
@@ -16,6 +16,7 @@ import yaml
 from ..attacks.l2_attacks import AutoAttack, CW, DeepFool
 from ..attacks.nes import NESAttack
 from ..attacks.pgd import PGDLinf
+from ..attacks.square import SquareAttack
 from ..defenses.ablations.models import GaussianBlurDefenseModel, GaussianNoiseDefenseModel
 from ..defenses.competitors.a_vae import AVaeDefenseModel, load_AVAE
 from ..defenses.competitors.nd_vae import NDVaeDefenseModel, load_NDVAE
@@ -72,6 +73,10 @@ def load(args: Namespace):
     nes_pairs = 64
     args.nes = NESAttack(norm='Linf', eps=8.0 / 255.0, step_size=2.0 / 255.0, steps=40, pairs=nes_pairs, sigma=1e-3,
                          query_images=max(1, (1024 * 64 * 64) // (args.image_size ** 2 * 2 * nes_pairs)))
+    # Square Attack, the other score-based black-box attack (attacks/square.py; not in the reference tree): L2 like the reference's
+    # attack sets, at the smallest AutoAttack bound of this tree; `--attack square` of experiments.seeded_defense.  One query row per
+    # image and iteration.
+    args.square = SquareAttack(norm='L2', eps=0.5, n_queries=5000)
 
     if args.defense_type in ('base', 'trades'):
         defense_model = base_classifier

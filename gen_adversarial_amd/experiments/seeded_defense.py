@@ -14,7 +14,8 @@ The draw number of a call counts the calls since the restart, so results are com
 Everything else — the torch seeds of the attacks' own starting points included — is test_defense's, except for NES (--attack nes):
 its directions and its starting point come from the same generator at rows (index of the image in the dataset) x pairs
 (`NESAttack.image_index`), so an image's queries are the same in every partition; the defender's own draws under its query calls
-count rows from the batch's first image.
+count rows from the batch's first image.  Square Attack (--attack square) likewise: its windows, signs and starting point are drawn
+at row (index of the image in the dataset) (`SquareAttack.image_index`).
 """
 from __future__ import annotations
 
@@ -32,8 +33,8 @@ import torch.distributed as dist
 from . import test_defense as drv
 
 
-OWN_ATTACKS = ('nes',)                                 # --attack choices of this driver beside test_defense's
-RESULT_KEYS = {**drv.RESULT_KEYS, 'nes': 'NES'}        # results.json column of each attack
+OWN_ATTACKS = ('nes', 'square')                       # --attack choices of this driver beside test_defense's
+RESULT_KEYS = {**drv.RESULT_KEYS, 'nes': 'NES', 'square': 'SQUARE'}   # results.json column of each attack
 
 
 def noise_owner(defense_model):
@@ -63,7 +64,7 @@ def evaluate_seeded(defense_model, attacks: Dict[str, Callable], images: torch.T
             out[lo:hi, 0] = t[:, 0]
             for j, k in enumerate(batched):
                 out[lo:hi, 1 + names.index(k)] = t[:, 1 + j]
-            # attacks with an `image_index` (NES) draw their own numbers by dataset index, and their calls hold query rows, not the
+            # attacks with an `image_index` (NES, Square Attack) draw their own numbers by dataset index, and their calls hold query rows, not the
             # batch's images: the defender's rows then count from the batch's first image, one draw per call from 0
             for k, a in indexed.items():
                 owner.seeded_noise(int(seed), draw=0, first_row=int(index_of(lo)) * eot)
@@ -124,11 +125,11 @@ def run_worker(rank: int, world: int, args, make_model: Callable, dataset: Tuple
 
 
 def parse_args(argv=None):
-    """test_defense's flags + --noise_seed; `--attack nes` is this driver's own choice and never reaches test_defense's parser"""
+    """test_defense's flags + --noise_seed; `--attack nes` / `--attack square` are this driver's own choices and never reach test_defense's parser"""
     argv = sys.argv[1:] if argv is None else list(argv)
     p = argparse.ArgumentParser(add_help=False)
     p.add_argument('--noise_seed', type=int, required=True, help='seed of the defender\'s draws (ga_randn)')
-    p.add_argument('--attack', type=str, default=None, help='test_defense\'s choices, or nes (black-box, attacks/nes.py)')
+    p.add_argument('--attack', type=str, default=None, help='test_defense\'s choices, or nes / square (black-box, attacks/nes.py, attacks/square.py)')
     own, rest = p.parse_known_args(argv)
     if own.attack is not None and own.attack not in OWN_ATTACKS:
         rest += ['--attack', own.attack]
@@ -155,6 +156,8 @@ def main():
             a.attacks = {'pgd-bpda': getattr(a, 'pgd_bpda', None) or type(a.pgd)(eps=a.pgd.eps, step_size=a.pgd.step_size, steps=a.pgd.steps, bpda=True)}
         elif a.attack == 'nes':
             a.attacks = {'nes': a.nes}
+        elif a.attack == 'square':
+            a.attacks = {'square': a.square}
         elif a.attack is not None:
             a.attacks = {k: v for k, v in a.attacks.items() if k == a.attack}
         return a, m

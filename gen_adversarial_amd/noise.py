@@ -14,6 +14,7 @@ import numpy as np
 
 STREAM_INPUT = 2147483648          # GA_RANDN_STREAM_INPUT: the input noise; latent group i draws with stream = i
 STREAM_NES = 2147483649            # GA_RANDN_STREAM_NES: the directions of the NES attack (attacks/nes_ref.py)
+STREAM_SQUARE = 2147483650         # GA_RANDN_STREAM_SQUARE: the windows, signs and orientations of Square Attack (attacks/square_ref.py)
 
 _M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
 _W0, _W1 = 0x9E3779B9, 0xBB67AE85

@@ -671,6 +671,47 @@ int ga_nes_grad(const float* c, float* g, long images, long inner, long pairs, u
                 unsigned long row0, const unsigned* image_row, float scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * ga_square_linf / ga_square_l2 — one proposal per image of Square Attack (Andriushchenko, Croce, Flammarion & Hein 2020;
+ * gen_adversarial_amd/attacks/square.py): every image of the launch gets its own window positions, signs and orientation from
+ * ga_randn's generator, so a proposal is a pure function of (seed, draw, image row, current iterate) that
+ * gen_adversarial_amd/attacks/square_ref.py restates in numpy.  Not plan ops: called directly, scalars like ga_nes_*.
+ *
+ * Random words of image b:  Wd = philox(c0 = 0, c1 = image_row[b], c2 = tensor, c3 = draw),  Vd = philox(c0 = 1, same c1..c3)
+ * (Philox4x32-10 keyed by the seed as in ga_randn; image_row a DEVICE array of `images` unsigned words, or NULL, which means
+ * image_row[b] = row0 + b).  Integer choices only, so that host and device agree bit for bit:
+ *     pos(word, n) = (word * n) >> 32 in 64-bit arithmetic, a number in [0, n)
+ *     window 1: rows h1 .. h1 + s - 1, columns w1 .. w1 + s - 1 with (h1, w1) = (pos(Wd0, H - s + 1), pos(Wd1, W - s + 1))
+ *     window 2 (L2 only): (h2, w2) = (pos(Vd0, H - s + 1), pos(Vd1, W - s + 1))
+ *     sign[ch] = +1 where bit ch of Wd2 is set, else -1;   the L2 bump is transposed where bit 0 of Wd3 is set.
+ * x_orig, x_adv, y: [images, C, H, W] fp32, y written; lo > hi: no clamp.
+ *
+ * ga_square_linf:  y[b] = x_adv[b] outside window 1;  inside, y[b, ch] = clamp(x_orig[b, ch] + sign[ch] * eps, lo, hi): one
+ *   rounding per element.  Grid-stride and store-bound like ga_nes_perturb: 16-byte accesses where W % 4 == 0 and the three
+ *   pointers are 16-byte aligned, the scalar path otherwise (no inner % 4 requirement, never GA_E_ALIGN).
+ * ga_square_l2:  eta: DEVICE table [s, s] of the bump (square_ref.eta(s): unit L2 norm).  Per image, with d = x_adv - x_orig:
+ *     n_img^2    = sum_{ch,h,w} d^2
+ *     n_win[ch]^2 = sum of d[ch]^2 over the UNION of the two windows
+ *     n_1        = norm of d over window 1, all channels
+ *     new[ch, i, j] = sign[ch] * (transposed ? eta[j, i] : eta[i, j]) + d[ch, h1 + i, w1 + j] / (1e-12 + n_1)
+ *     scale[ch]  = sqrt(max(eps^2 - n_img^2, 0) / C + n_win[ch]^2) / (1e-12 + norm of new[ch])
+ *     d' = d;  d' = 0 in window 2;  then d'[ch] = scale[ch] * new[ch] in window 1 (window 1 wins where they overlap)
+ *     y = clamp(x_orig + d' * eps / (1e-12 + norm of d'), lo, hi)
+ *   One workgroup of 256 threads per image walks the pixels in strides; every sum is a strided per-thread partial, a wave-64
+ *   __shfl_xor butterfly, and the four waves' partials added in wave order through LDS: one fixed order, no atomics, so an
+ *   image's bits do not depend on the batch around it.  The same code serves 3 x 8 x 8 and 3 x 256 x 256.
+ * GA_E_BADARG: a NULL x_orig, x_adv, y (or eta); images, C, H, W <= 0; s < 1 or s > min(H, W); a row past 2^32 (image_row NULL:
+ *   row0 + images > 2^32);  GA_E_UNSUPPORTED: C > 32 (one sign bit per channel), C * H * W >= 2^31, ga_square_l2: more than
+ *   2^31 - 1 images (the grid).
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define GA_RANDN_STREAM_SQUARE 2147483650  /* counter word 2 of Square Attack's choices */
+int ga_square_linf(const float* x_orig, const float* x_adv, float* y, long images, int C, int H, int W, int s, unsigned long seed,
+                   unsigned draw, unsigned tensor, unsigned long row0, const unsigned* image_row, float eps, float lo, float hi,
+                   void* stream);
+int ga_square_l2(const float* x_orig, const float* x_adv, float* y, const float* eta, long images, int C, int H, int W, int s,
+                 unsigned long seed, unsigned draw, unsigned tensor, unsigned long row0, const unsigned* image_row, float eps, float lo,
+                 float hi, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Plans: a forward or backward pass is a flat list of the ops above, built once on the host and replayed by ONE call.
  * ------------------------------------------------------------------------------------------------------------------ */
 typedef struct ga_axpby_desc { const float* x; float* y; long n; float alpha, beta; } ga_axpby_desc;
@@ -756,6 +797,7 @@ const char* ga_last_hip_error(void);
  * looks every declared symbol up when it loads, so a library built before ga_randn existed is refused by name: the version stays.) */
 /* (ga_nes_perturb and ga_nes_grad likewise: entry points of their own with scalar arguments, no descriptor, ga_op untouched, and a
  * library without them is refused by name when the binding looks them up: the version stays.) */
+/* (ga_square_linf and ga_square_l2 likewise.) */
 #define GA_ABI_VERSION 8
 int ga_abi_version(void);
 unsigned long ga_sizeof_op(void);
