@@ -396,7 +396,7 @@ extern "C" int ga_dwconv5(const ga_dwconv5_desc* dp, void* stream_) {
 
     const int nchunks = (d.C + DW_CC - 1) / DW_CC;
     if (d.H == 4 && d.W == 4 && !d.up2 && !d.pool2) {
-        const long blocks = (long)((d.N + 15) / 16) * nchunks;
+        const long blocks = (((long)d.N + 15) / 16) * nchunks;                 // N + 15 in 64 bits: N may be INT_MAX
         if (blocks > 0x7fffffffL) return GA_E_UNSUPPORTED;
         hipLaunchKernelGGL(dwconv5_4x4_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, d, nchunks);
         return check_launch();
@@ -417,7 +417,7 @@ extern "C" int ga_dwconv5(const ga_dwconv5_desc* dp, void* stream_) {
         if (NB < 1) NB = 1;
         const int plane = ((NB * HH * WW * 16 + 63) & ~63) + 16;        // floats: a multiple of 256 B plus 64 B
         const int tilesH = (Hs + TH - 1) / TH, tilesW = (Ws + TW - 1) / TW;
-        const long blocks = (long)((d.N + NB - 1) / NB) * tilesH * tilesW * nchunks;
+        const long blocks = (((long)d.N + NB - 1) / NB) * tilesH * tilesW * nchunks;
         if (blocks > 0x7fffffffL) return GA_E_UNSUPPORTED;
         const size_t lds = (size_t)(25 * DW_CC + 2 * plane) * 4;
         hipLaunchKernelGGL(dwconv5_up2_kernel, dim3((unsigned)blocks), dim3(256), lds, stream, d, NB, TH, TW, WW, plane, tilesH, tilesW, nchunks);
@@ -433,7 +433,7 @@ extern "C" int ga_dwconv5(const ga_dwconv5_desc* dp, void* stream_) {
     if (NB > d.N) NB = d.N;
     if (NB < 1) NB = 1;
     const int tilesH = (d.H + TH - 1) / TH, tilesW = (d.W + TW - 1) / TW;
-    const long blocks = (long)((d.N + NB - 1) / NB) * tilesH * tilesW * nchunks;
+    const long blocks = (((long)d.N + NB - 1) / NB) * tilesH * tilesW * nchunks;
     if (blocks > 0x7fffffffL) return GA_E_UNSUPPORTED;
     const size_t lds = (size_t)NB * halo_bytes + 25 * DW_CC * 4;
     // strips of 4 when every tile width is a multiple of 4 (the strip reads SW+4 columns: stays inside the halo),

@@ -1314,7 +1314,7 @@ extern "C" int ga_rowchan_reduce(const ga_rowchan_reduce_desc* d, void* s) {
     if (!d->a && (!aligned16(d->a_src) || !aligned16(d->a_w))) return GA_E_ALIGN;
     if (d->scaled && (!d->gate || !aligned16(d->scaled) || !aligned16(d->gate) || (d->skip && !aligned16(d->skip)))) return GA_E_BADARG;
     const int nchunks = (d->C + 63) / 64;
-    if (d->ws && d->P >= 4096 && d->N * nchunks < 1024) {
+    if (d->ws && d->P >= 4096 && (long)d->N * nchunks < 1024) {
         if (!aligned16(d->ws)) return GA_E_ALIGN;
         long S = d->ws_floats / ((long)d->N * d->C);
         const long want = 2048 / ((long)d->N * nchunks);                 // ~8 workgroups per CU
@@ -1332,7 +1332,8 @@ extern "C" int ga_rowchan_reduce(const ga_rowchan_reduce_desc* d, void* s) {
             return check_launch();
         }
     }
-    hipLaunchKernelGGL(rowchan_reduce_kernel, dim3(d->N * nchunks), dim3(256), 0, (hipStream_t)s, *d, nchunks);
+    if ((long)d->N * nchunks > 0x7fffffffL) return GA_E_UNSUPPORTED;     // one workgroup per (row, 64-channel chunk)
+    hipLaunchKernelGGL(rowchan_reduce_kernel, dim3((unsigned)((long)d->N * nchunks)), dim3(256), 0, (hipStream_t)s, *d, nchunks);
     return check_launch();
 }
 
@@ -1486,7 +1487,8 @@ extern "C" int ga_modout(const ga_modout_desc* d, void* s) {
         int ql = 1;
         while (ql < q) ql <<= 1;
         const int seg_len = (int)((d->P + S - 1) / S);
-        hipLaunchKernelGGL(modout_bwd_reduce_kernel, dim3((unsigned)(d->N * nchunks * S)), dim3(256), 0, (hipStream_t)s, *d, nchunks, ql,
+        if ((long)d->N * nchunks * S > 0x7fffffffL) return GA_E_UNSUPPORTED;             // one workgroup per (row, chunk, segment)
+        hipLaunchKernelGGL(modout_bwd_reduce_kernel, dim3((unsigned)((long)d->N * nchunks * S)), dim3(256), 0, (hipStream_t)s, *d, nchunks, ql,
                            (int)S, seg_len);
         ga_rowchan_reduce_desc r = {};
         r.out = d->red; r.N = d->N; r.P = d->P; r.C = d->C; r.scale = 1.0f; r.ws = d->ws; r.ws_floats = d->ws_floats;
@@ -1598,7 +1600,8 @@ extern "C" int ga_avgpool_act(const ga_avgpool_act_desc* d, void* s) {
     if (d->backward && (!d->dy || !d->dx)) return GA_E_BADARG;
     if (d->act_rep > 1 && (!d->backward || d->N % d->act_rep)) return GA_E_BADARG;
     const int nchunks = (d->C + 63) / 64;
-    hipLaunchKernelGGL(avgpool_act_kernel, dim3(d->N * nchunks), dim3(256), 0, (hipStream_t)s, *d, nchunks);
+    if ((long)d->N * nchunks > 0x7fffffffL) return GA_E_UNSUPPORTED;     // one workgroup per (row, 64-channel chunk)
+    hipLaunchKernelGGL(avgpool_act_kernel, dim3((unsigned)((long)d->N * nchunks)), dim3(256), 0, (hipStream_t)s, *d, nchunks);
     return check_launch();
 }
 

@@ -124,6 +124,8 @@ int ga_conv2d(const ga_conv_desc* d, void* stream);
  *                                                        read — nn.UpsamplingNearest2d commutes with the 1x1/BN/SiLU
  *                                                        in front of it, architecture.py:162-168)
  *   backward: y = dw5_flipped(x) * act'_dact(dact_x)    with `pool2`: the 2x2 sum that is the adjoint of `up2`
+ * Every row offset is formed in 64 bits (tensors past 2^32 bytes: tests/test_large_extent_gpu.py); a launch that would need more
+ * than 2^31 - 1 workgroups (row blocks x tiles x 32-channel chunks) is refused with GA_E_UNSUPPORTED, for any N up to INT_MAX.
  * ------------------------------------------------------------------------------------------------------------------ */
 typedef struct ga_dwconv5_desc {
     const float* x;      /* [N,Hs,Ws,C]; Hs = H/2 if up2 else H */
@@ -144,7 +146,8 @@ int ga_dwconv5(const ga_dwconv5_desc* d, void* stream);
 /* out[n,c] = scale * sum_p a[n,p,c] * (b ? b[n,p,c] : 1)      (squeeze: scale=1/HW; d(gate): b = t, scale = 0.1)
  * ws (optional, ws_floats >= 2*N*C): workspace for a two-stage reduction — the pixels of a row are split over up to
  * ws_floats / (N*C) workgroups and the partial sums added in a fixed order (StyleGAN2 style gradients: 1024^2 pixels, 32
- * channels, a handful of rows).  Without it one workgroup per (row, 64 channels) walks all P pixels. */
+ * channels, a handful of rows).  Without it one workgroup per (row, 64 channels) walks all P pixels.
+ * GA_E_UNSUPPORTED: N * ceil(C / 64) > 2^31 - 1 (the grid; the product is formed in 64 bits). */
 typedef struct ga_rowchan_reduce_desc {
     const float* a; const float* b; float* out;
     int N, P, C; float scale;
@@ -311,7 +314,8 @@ int ga_unary(const ga_unary_desc* d, void* stream);
 /* StyledConv's tail (generator.py:258-265: demodulation folded out of the weights, NoiseInjection, FusedLeakyReLU):
  *   forward : out[n,p,c] = act(u),  u = scale[n,c] * t[n,p,c] + add[p,c]        (scale / add may be NULL = 1 / 0)
  *   backward: dt[n,p,c]  = dout * act'(u) * scale[n,c]                          (u recomputed from t)
- * t, out, dout, dt: [N,P,C]; scale: [N,C]; add: [P,C] (noise strength * noise[p] + bias[c], row independent). C % 4 == 0. */
+ * t, out, dout, dt: [N,P,C]; scale: [N,C]; add: [P,C] (noise strength * noise[p] + bias[c], row independent). C % 4 == 0.
+ * With `red`: GA_E_UNSUPPORTED when N * ceil(C / 64) * segments > 2^31 - 1 (the grid). */
 typedef struct ga_modout_desc {
     const float* t; const float* scale; const float* add; float* out; const float* dout; float* dt;
     int N, P, C; int act; int backward;
@@ -520,7 +524,8 @@ typedef struct ga_maxpool3s2_desc {
 int ga_maxpool3s2(const ga_maxpool3s2_desc* d, void* stream);
 
 /* Global average pool with an activation prologue (torchvision ResNet `avgpool` after the last block's ReLU):
- * forward  y[n,c] = mean_p act(x[n,p,c]);  backward dx[n,p,c] = dy[n,c] / P * act'(x[n,p,c]).  x: [N,P,C], C % 4 == 0. */
+ * forward  y[n,c] = mean_p act(x[n,p,c]);  backward dx[n,p,c] = dy[n,c] / P * act'(x[n,p,c]).  x: [N,P,C], C % 4 == 0.
+ * GA_E_UNSUPPORTED: N * ceil(C / 64) > 2^31 - 1 (the grid). */
 typedef struct ga_avgpool_act_desc {
     const float* x; float* y; const float* dy; float* dx; int N, P, C; int act; int backward;
     int act_rep;      /* backward, > 1: N counts cotangent rows (dy, dx); x has N/act_rep rows, cotangent row n reads x row

@@ -19,6 +19,8 @@ Entry points and fields that are not tested here:
   tests/test_dec_cell_f64_gpu.py, tests/test_dec_cell_halo_f64_gpu.py   the same two row by row against the float64 cell of
                                 tests/cellref.py: every accepted geometry, the chunk pipeline, act_rep, aliased addends,
                                 bit equality with the unfused launches, refusals
+  tests/test_large_extent_gpu.py    every non-conv op, the fused cells included, with its largest operand past 2^32 bytes and, wherever
+                                48 GB hold the case, past 2^31 elements: one launch against its row chunks, bit for bit (tests/bigrows.py)
   tests/test_alpha_search_gpu.py                                    per-row alpha tables of ga_sampler_mix / ga_latent_mix
   tests/test_stylegan_gpu.py, tests/test_trans_gpu.py, tests/test_resnet_gpu.py   ga_up2_blur, ga_attn, ga_layernorm,
                                 ga_resize2_crop and the remaining pieces inside their models
