@@ -75,6 +75,10 @@ static int validate(const ga_conv_desc& d) {
 // ga_debug_set_conv_row_limit so that tests reach the sub-batch path at small sizes
 static long g_conv_row_limit = 0x7fffff00L;
 
+// what ga_conv2d decides about a descriptor before it launches (conv_resolve, below)
+struct conv_choice { ga_conv_desc k; conv_req r; const conv_family* family; long M; };
+static int conv_resolve(const ga_conv_desc& d, conv_choice* out);
+
 // Rows are independent: a tensor beyond the fast loader's 31-bit byte offsets (2 GB; StyleGAN2's 1024^2 x 32-channel maps
 // at a few dozen rows) is convolved in sub-batches of rows that fit, each an ordinary launch on the same stream.
 // Returns false when d needs no cutting; else rc is the call's result.
@@ -91,11 +95,24 @@ static bool run_in_row_batches(const ga_conv_desc& d, void* stream, int& rc) {
     int sub = (int)((lim - 1) / row_max);
     const int arep = d.addend && !d.addend_bcast_n && d.addend_rep > 1 ? d.addend_rep : 1;
     const int drep = d.dact_x && d.dact_rep > 1 ? d.dact_rep : 1;
-    if (arep > 1 || drep > 1) {                      // operands shared by consecutive rows: cut at their row boundaries
-        const long both = (long)arep * drep;         // (a common multiple; the two never meet on one launch in practice)
+    const long both = (long)arep * drep;             // operands shared by consecutive rows: cut at their row boundaries
+    if (arep > 1 || drep > 1) {                      // (a common multiple; the two never meet on one launch in practice)
         if (d.N % arep || d.N % drep) { rc = GA_E_BADARG; return true; }
         sub -= (int)(sub % both);
         if (sub < both) { rc = GA_E_UNSUPPORTED; return true; }
+    }
+    // The explicit tiles have a row granularity of their own (tile 9: whole groups of 32 images, tile 12: whole 128-pixel tiles).  A
+    // cut on a multiple of 128 rows keeps both for any Ho * Wo, in the sub-batches and in the remainder of an N that had it: a
+    // descriptor a family takes at a small N is not refused for its size.  Rows so large that fewer than 128 fit keep the cut above
+    // (documented with ga_conv2d in ga_ops.h).
+    if (sub >= 128 * both) sub -= (int)(sub % (128 * both));
+    // Among the fields that differ between sub-batches a refusal depends on the row count alone (the pointers advance by whole rows
+    // of pitches that keep their 16-byte class): ask for the two row counts there are before anything is enqueued, so that a call
+    // that returns an error has written nothing
+    for (const int n : {sub, d.N % sub}) {
+        ga_conv_desc s = d;
+        s.N = n;
+        if (n > 0 && (rc = conv_resolve(s, nullptr)) != GA_OK) return true;
     }
     for (int n0 = 0; n0 < d.N; n0 += sub) {
         ga_conv_desc s = d;
@@ -177,6 +194,28 @@ static int reduce_split_k(const ga_conv_desc& k, const long M, const conv_req& r
     return check_launch();
 }
 
+// everything ga_conv2d decides about a descriptor that needs no cutting, without enqueuing: the split-K factor, the operand
+// classes, the tile and the family whose check accepts it (out, when given); the refusal code otherwise
+static int conv_resolve(const ga_conv_desc& d, conv_choice* out) {
+    int splits = 1;
+    int rc = split_factor(d, splits);
+    if (rc != GA_OK) return rc;
+    conv_choice c;
+    c.M = (long)d.N * d.Ho * d.Wo;
+    c.k = d;
+    c.r = operand_classes(d, splits, c.k);
+    if (c.r.tile == 0) c.r.tile = heuristic_tile(d, c.M);
+    rc = GA_E_UNSUPPORTED;
+    for (const conv_family& f : CONV_FAMILIES) {
+        if (c.r.tile < f.tile_lo || c.r.tile > f.tile_hi) continue;
+        if ((rc = f.check(c.k, c.r)) != GA_OK) continue;
+        c.family = &f;
+        break;
+    }
+    if (rc == GA_OK && out) *out = c;
+    return rc;
+}
+
 }  // namespace ga
 
 extern "C" long ga_debug_set_conv_row_limit(long bytes) {
@@ -191,23 +230,14 @@ extern "C" int ga_conv2d(const ga_conv_desc* dp, void* stream_) {
     if (!dp) return GA_E_BADARG;
     const ga_conv_desc& d = *dp;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    int rc = validate(d), splits = 1;
+    int rc = validate(d);
     if (rc != GA_OK) return rc;
     if (run_in_row_batches(d, stream_, rc)) return rc;
-    if ((rc = split_factor(d, splits)) != GA_OK) return rc;
-    const long M = (long)d.N * d.Ho * d.Wo;
-    ga_conv_desc k = d;
-    conv_req r = operand_classes(d, splits, k);
-    if (r.tile == 0) r.tile = heuristic_tile(d, M);
-    rc = GA_E_UNSUPPORTED;
-    for (const conv_family& f : CONV_FAMILIES) {
-        if (r.tile < f.tile_lo || r.tile > f.tile_hi) continue;
-        if ((rc = f.check(k, r)) != GA_OK) continue;
-        rc = f.launch(k, r, stream);
-        break;
-    }
-    if (rc != GA_OK || splits == 1) return rc;
-    return reduce_split_k(k, M, r, stream);
+    conv_choice c;
+    if ((rc = conv_resolve(d, &c)) != GA_OK) return rc;
+    rc = c.family->launch(c.k, c.r, stream);
+    if (rc != GA_OK || c.r.splits == 1) return rc;
+    return reduce_split_k(c.k, c.M, c.r, stream);
 }
 
 extern "C" int ga_split_bf16(const float* w, void* hi, void* lo, long n, void* stream) {

@@ -61,6 +61,16 @@ enum ga_conv_flags { GA_CONV_ADDEND_RELU = 1, GA_CONV_ADDEND_PRE_DACT = 2, GA_CO
  * addend may alias y (in-place accumulation of a gradient).
  * splits > 1: K is cut into `splits` slices computed by separate workgroups into `ws`, then summed in slice order
  * (deterministic) by a second kernel that applies the epilogue — for small N*Ho*Wo*Cout with a long K.
+ * Extents: once x, x2, y, addend (unless addend_bcast_n), addend2 or dact_x, counted with its pitch, reaches 0x7fffff00 bytes (the
+ * 31-bit byte offsets of the fast loaders), the call is carried out as consecutive sub-batches of rows that stay below it, each an
+ * ordinary launch on the same stream; rows are independent, the results are those of one launch.  The broadcast addend and the split-K
+ * workspace (which needs splits * rows-of-a-sub-batch * Ho*Wo*Cout floats only) are not counted.  The cut is a multiple of addend_rep *
+ * dact_rep (N % rep != 0 is GA_E_BADARG, a cut of fewer rows than that GA_E_UNSUPPORTED) and, where 128 * that many rows fit, of 128
+ * rows, which keeps tile 9's groups of 32 images and tile 12's 128-pixel tiles whole: a descriptor a tile takes at a small N is not
+ * refused for its size.  Rows above 16 MB (fewer than 128 per sub-batch) are cut at the replica multiple alone; tile 12 then refuses
+ * (GA_E_UNSUPPORTED) a tensor whose sub-batch is not a multiple of 128 pixels.  Every sub-batch is checked before the first is
+ * launched: a call that returns an error has written nothing.  One row at or above the limit (N == 1) runs on the fp32 kernel's
+ * plain-load path, whatever w_hi / w_lo say; explicit tiles 5 - 12 refuse it.
  * ------------------------------------------------------------------------------------------------------------------ */
 typedef struct ga_conv_desc {
     const float* x;          int ldx;      /* [N,Hi,Wi,ldx], channels [0,C1) used */

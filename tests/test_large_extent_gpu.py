@@ -50,7 +50,7 @@ the tiers an entry point reaches with at least one mode.
   ga_resize2_crop        T2 T3  forward; backward
   ga_avae                T2 T3  ADAIN, AVGPOOL, PIXELNORM, SAMPLE, forward and backward (act_rep)
   ga_dwconv5             T2 T3  plain, 4 x 4, flipped with pool2 / dact_x / act_rep, up2
-  ga_conv2d              conv: see test_ops_gpu.py (test_conv_beyond_2gb_runs_in_row_sub_batches and its neighbour)
+  ga_conv2d              conv: tests/test_conv_large_extent_gpu.py (every family at and past 2 GB; tests/convbig.py)
   ga_dec_cell            T2 T3  every accepted (H, W, C) class (cellref.GEOMS) at Hd = 32 (one hidden chunk) and 96 (three), one per C at the
                                 shipped Hd = 6 C; forward, backward with act_rep; variant 1 at every C = 128 class with Hd = 96.
                                 Operand table: bigrows.CellModel; the first chunk is held to cellref's row-wise bound

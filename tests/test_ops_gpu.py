@@ -21,6 +21,8 @@ Entry points and fields that are not tested here:
                                 bit equality with the unfused launches, refusals
   tests/test_large_extent_gpu.py    every non-conv op, the fused cells included, with its largest operand past 2^32 bytes and, wherever
                                 48 GB hold the case, past 2^31 elements: one launch against its row chunks, bit for bit (tests/bigrows.py)
+  tests/test_conv_large_extent_gpu.py   ga_conv2d, every kernel family, with its largest counted operand at the 2 GB limit and past 2^31 /
+                                2^32 bytes: one call against its row chunks, bit for bit (tests/convbig.py)
   tests/test_alpha_search_gpu.py                                    per-row alpha tables of ga_sampler_mix / ga_latent_mix
   tests/test_stylegan_gpu.py, tests/test_trans_gpu.py, tests/test_resnet_gpu.py   ga_up2_blur, ga_attn, ga_layernorm,
                                 ga_resize2_crop and the remaining pieces inside their models
