@@ -334,7 +334,7 @@ using namespace ga;
 
 extern "C" int ga_attn(const ga_attn_desc* d, void* s) {
     ga::clear_stale_error();
-    if (!d || !d->q || !d->k || !d->v || !d->p || d->N <= 0 || d->Tk <= 0 || d->heads <= 0) return GA_E_BADARG;
+    if (!d || !d->q || !d->k || !d->v || !d->p || d->N <= 0 || d->Tk <= 0 || d->heads <= 0 || d->dh <= 0) return GA_E_BADARG;
     // 16 style queries, 512 / 4 heads = 128 channels per head (style_transformer_encoders.py:37-41); reduced widths down to 16
     if (d->Tq != ATT_TQ || d->dh > 128 || d->dh % 16) return GA_E_UNSUPPORTED;
     if ((d->ldq | d->ldk | d->ldv | d->ldo) % 4) return GA_E_UNSUPPORTED;

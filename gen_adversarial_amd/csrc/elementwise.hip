@@ -1312,7 +1312,8 @@ extern "C" int ga_rowchan_reduce(const ga_rowchan_reduce_desc* d, void* s) {
     if (d->C % 4) return GA_E_UNSUPPORTED;
     if ((d->a && !aligned16(d->a)) || !aligned16(d->out) || (d->b && !aligned16(d->b))) return GA_E_ALIGN;
     if (!d->a && (!aligned16(d->a_src) || !aligned16(d->a_w))) return GA_E_ALIGN;
-    if (d->scaled && (!d->gate || !aligned16(d->scaled) || !aligned16(d->gate) || (d->skip && !aligned16(d->skip)))) return GA_E_BADARG;
+    if ((d->scaled != nullptr) != (d->gate != nullptr)) return GA_E_BADARG;                  // the second output and its gate come together
+    if (d->scaled && (!aligned16(d->scaled) || !aligned16(d->gate) || (d->skip && !aligned16(d->skip)))) return GA_E_ALIGN;
     const int nchunks = (d->C + 63) / 64;
     if (d->ws && d->P >= 4096 && (long)d->N * nchunks < 1024) {
         if (!aligned16(d->ws)) return GA_E_ALIGN;
@@ -1342,7 +1343,8 @@ extern "C" int ga_se_excite(const ga_se_excite_desc* d, void* s) {
     if (!d || !d->w1 || !d->b1 || !d->w2 || !d->b2 || !d->hid || !d->gate || d->N <= 0 || d->C <= 0 || d->Hd <= 0) return GA_E_BADARG;
     if (!d->backward && !d->m && !d->t) return GA_E_BADARG;
     if (d->backward && ((!d->dgate && !d->t) || !d->pro_scale || !d->pro_shift || d->P <= 0)) return GA_E_BADARG;
-    if (d->out && (d->backward || !d->t || !aligned16(d->out) || (d->skip && !aligned16(d->skip)))) return GA_E_BADARG;
+    if (d->out && (d->backward || !d->t)) return GA_E_BADARG;
+    if (d->out && (!aligned16(d->out) || (d->skip && !aligned16(d->skip)))) return GA_E_ALIGN;
     if (d->act_rep > 1 && (!d->backward || !d->t || d->N % d->act_rep)) return GA_E_BADARG;
     size_t lds = (size_t)(d->C + d->Hd + 4 + 256) * sizeof(float);     // + [Hd][chunks] partials of the FC phases
     if (d->Hd > 256) return GA_E_UNSUPPORTED;
@@ -1397,8 +1399,9 @@ extern "C" int ga_sampler_mix(const ga_sampler_desc* d, void* s) {
     ga::clear_stale_error();
     if (d && d->mode == 2) return sampler_alpha_grad(d, s);
     if (!d || !d->mu_q || !d->eps || d->N <= 0 || d->h <= 0 || d->w <= 0 || d->NL <= 0) return GA_E_BADARG;
-    if (d->ldq < d->NL || (d->p && d->ldp < 2 * d->NL)) return GA_E_BADARG;
+    if (d->ldq < d->NL || (d->p && d->ldp < 2 * d->NL) || (d->ldz != 0 && d->ldz < d->NL)) return GA_E_BADARG;
     if (!d->backward && !d->z) return GA_E_BADARG;
+    if (d->dp && !d->p) return GA_E_BADARG;                             // dp is written under ldp, which is only held to 2 NL with p
     if (d->backward && (!d->dz || (d->q_rep > 1 ? !d->dmu_q_rows : !d->dmu_q) || (d->p && !d->dp))) return GA_E_BADARG;
     if (d->q_rep > 1 && d->N % d->q_rep) return GA_E_BADARG;
     if (d->act_rep > 1 && (!d->backward || d->N % d->act_rep || (d->q_rep > 1 && (d->N / d->act_rep) % d->q_rep))) return GA_E_BADARG;
@@ -1435,6 +1438,7 @@ extern "C" int ga_maxpool2(const ga_maxpool2_desc* d, void* s) {
     if (!d->backward && !d->y) return GA_E_BADARG;
     if (d->backward && (!d->dy || !d->dx)) return GA_E_BADARG;
     if (d->act_rep > 1 && (!d->backward || d->N % d->act_rep)) return GA_E_BADARG;
+    if (!aligned16(d->x) || (d->backward ? !aligned16(d->dy) || !aligned16(d->dx) : !aligned16(d->y))) return GA_E_ALIGN;
     const long total4 = (long)d->N * (d->H / 2) * (d->W / 2) * (d->C / 4);
     hipLaunchKernelGGL(maxpool2_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)s, *d, total4);
     return check_launch();
@@ -1447,6 +1451,7 @@ extern "C" int ga_maxpool3s2(const ga_maxpool3s2_desc* d, void* s) {
     if (!d->backward && !d->y) return GA_E_BADARG;
     if (d->backward && (!d->dy || !d->dx)) return GA_E_BADARG;
     if (d->act_rep > 1 && (!d->backward || d->N % d->act_rep)) return GA_E_BADARG;
+    if (!aligned16(d->x) || (d->backward ? !aligned16(d->dy) || !aligned16(d->dx) : !aligned16(d->y))) return GA_E_ALIGN;
     const long total4 = d->backward ? (long)d->N * d->H * d->W * (d->C / 4) : (long)d->N * (d->H / 2) * (d->W / 2) * (d->C / 4);
     hipLaunchKernelGGL(maxpool3s2_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)s, *d, total4);
     return check_launch();
@@ -1470,13 +1475,18 @@ extern "C" int ga_modout(const ga_modout_desc* d, void* s) {
         if (d->backward && d->dt_planes[0] && (!d->dt_planes[1] || !d->dt_planes[2] || !d->dt_planes[3])) return GA_E_BADARG;
         if (d->t_planes[0] && (!d->t_planes[1] || !d->t_planes[2] || !d->t_planes[3])) return GA_E_BADARG;
         if (d->W <= 0 || d->W % 2 || d->P % d->W || (d->P / d->W) % 2) return GA_E_BADARG;
+        if (d->ld_planes != 0 && d->ld_planes < d->C) return GA_E_BADARG;
         if (d->ld_planes % 4) return GA_E_UNSUPPORTED;
         for (int i = 0; i < 4; ++i)
             if ((d->t_planes[0] && !aligned16(d->t_planes[i])) || (d->backward && d->dt_planes[0] && !aligned16(d->dt_planes[i]))) return GA_E_ALIGN;
     }
+    {
+        const void* ptrs[] = {d->t, d->scale, d->add, d->backward ? nullptr : d->out, d->backward ? d->dout : nullptr, d->backward ? d->dt : nullptr};
+        for (const void* p : ptrs) if (p && !aligned16(p)) return GA_E_ALIGN;                 // all read / written 16 bytes per lane
+    }
     if (d->backward && d->red) {
         if (!d->ws || d->ws_floats < (long)d->N * d->C) return GA_E_BADARG;
-        if (!aligned16(d->ws) || (d->t && !aligned16(d->t)) || !aligned16(d->dout) || (d->dt && !aligned16(d->dt))) return GA_E_ALIGN;
+        if (!aligned16(d->ws)) return GA_E_ALIGN;
         const int nchunks = (d->C + 63) / 64;
         long S = d->ws_floats / ((long)d->N * d->C);
         const long want = (2048 + (long)d->N * nchunks - 1) / ((long)d->N * nchunks);     // ~8 workgroups per CU
@@ -1507,6 +1517,7 @@ extern "C" int ga_up2_blur(const ga_up2_blur_desc* d, void* s) {
     if (d->C % 4) return GA_E_UNSUPPORTED;
     if (!d->backward && (!d->lo_in || !d->hi)) return GA_E_BADARG;
     if (d->backward && (!d->hi_in || !d->lo)) return GA_E_BADARG;
+    if (d->backward ? !aligned16(d->hi_in) || !aligned16(d->lo) : !aligned16(d->lo_in) || !aligned16(d->hi)) return GA_E_ALIGN;
     const long total4 = (long)d->N * d->H * d->W * (d->C / 4) * (d->backward ? 1 : 4);
     hipLaunchKernelGGL(up2_blur_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)s, *d, total4);
     return check_launch();
@@ -1534,12 +1545,14 @@ static int latent_alpha_grad(const ga_latent_mix_desc* d, void* s) {
 extern "C" int ga_latent_mix(const ga_latent_mix_desc* d, void* s) {
     ga::clear_stale_error();
     if (d && d->backward == 2) return latent_alpha_grad(d, s);
-    if (!d || !d->alpha || d->R <= 0 || d->J <= 0 || d->D <= 0) return GA_E_BADARG;
+    if (!d || !d->alpha || d->R <= 0 || d->J <= 0 || d->D <= 0 || d->backward < 0 || d->backward > 2) return GA_E_BADARG;
     if (d->D % 4) return GA_E_UNSUPPORTED;
     if (!d->backward && (!d->codes || !d->styles || !d->out)) return GA_E_BADARG;
     if (d->backward && (!d->dout || !d->dcodes)) return GA_E_BADARG;
     if (d->rep > 1 && d->R % d->rep) return GA_E_BADARG;
     if (d->alpha_ld != 0 && d->alpha_ld < d->J) return GA_E_BADARG;
+    if (d->backward ? !aligned16(d->dout) || !aligned16(d->dcodes)
+                    : !aligned16(d->codes) || !aligned16(d->styles) || !aligned16(d->out) || (d->avg && !aligned16(d->avg))) return GA_E_ALIGN;
     const long total4 = (long)(d->backward && d->rep > 1 ? d->R / d->rep : d->R) * d->J * (d->D / 4);
     hipLaunchKernelGGL(latent_mix_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)s, *d, total4);
     return check_launch();
@@ -1551,6 +1564,7 @@ extern "C" int ga_pool_denorm(const ga_pool_denorm_desc* d, void* s) {
     if ((d->H | d->W) & 1 || d->ld % 4) return GA_E_UNSUPPORTED;
     if (!d->backward && (!d->x || !d->y)) return GA_E_BADARG;
     if (d->backward && (!d->dy || !d->dx)) return GA_E_BADARG;
+    if (d->backward ? !aligned16(d->dy) || !aligned16(d->dx) : !aligned16(d->x) || !aligned16(d->y)) return GA_E_ALIGN;
     const long total = (long)d->N * d->H * d->W * (d->backward ? d->k * d->k : 1);
     hipLaunchKernelGGL(pool_denorm_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, *d, total);
     return check_launch();
@@ -1562,6 +1576,7 @@ extern "C" int ga_prelu(const ga_prelu_desc* d, void* s) {
     if (d->C % 4) return GA_E_UNSUPPORTED;
     if (!d->backward && !d->y) return GA_E_BADARG;
     if (d->backward && (!d->dy || !d->dx)) return GA_E_BADARG;
+    if (!aligned16(d->x) || !aligned16(d->slope) || (d->backward ? !aligned16(d->dy) || !aligned16(d->dx) : !aligned16(d->y))) return GA_E_ALIGN;
     const long total4 = d->rows * (d->C / 4);
     hipLaunchKernelGGL(prelu_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)s, *d, total4);
     return check_launch();
@@ -1599,6 +1614,7 @@ extern "C" int ga_avgpool_act(const ga_avgpool_act_desc* d, void* s) {
     if (!d->backward && !d->y) return GA_E_BADARG;
     if (d->backward && (!d->dy || !d->dx)) return GA_E_BADARG;
     if (d->act_rep > 1 && (!d->backward || d->N % d->act_rep)) return GA_E_BADARG;
+    if (!aligned16(d->x) || (d->backward ? !aligned16(d->dy) || !aligned16(d->dx) : !aligned16(d->y))) return GA_E_ALIGN;
     const int nchunks = (d->C + 63) / 64;
     if ((long)d->N * nchunks > 0x7fffffffL) return GA_E_UNSUPPORTED;     // one workgroup per (row, 64-channel chunk)
     hipLaunchKernelGGL(avgpool_act_kernel, dim3((unsigned)((long)d->N * nchunks)), dim3(256), 0, (hipStream_t)s, *d, nchunks);
@@ -1655,6 +1671,13 @@ extern "C" int ga_interleave2(const ga_interleave2_desc* d, void* s) {
     if (((d->H | d->W) & 1) || (d->C % 4)) return GA_E_UNSUPPORTED;
     if ((d->dact_scale == nullptr) != (d->dact_shift == nullptr) && !d->dact_prelu) return GA_E_BADARG;
     if (d->dact_prelu && (!d->dact_x || !d->dact_scale)) return GA_E_BADARG;
+    if (d->dact_x && d->dact_rep > 1 && d->N % d->dact_rep) return GA_E_BADARG;             // row n reads dact_x row n / dact_rep
+    if (d->lds != 0 && d->lds < d->C) return GA_E_BADARG;
+    if (d->lds % 4) return GA_E_UNSUPPORTED;                                                 // the sources are read 16 bytes per lane
+    {
+        const void* ptrs[] = {d->s[0][0], d->s[0][1], d->s[1][0], d->s[1][1], d->y, d->dact_x, d->dact_scale, d->dact_shift, d->addend, d->addend2};
+        for (const void* p : ptrs) if (p && !aligned16(p)) return GA_E_ALIGN;
+    }
     const long total4 = (long)d->N * d->H * d->W * (d->C / 4);
     hipLaunchKernelGGL(interleave2_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)s, *d, total4);
     return check_launch();

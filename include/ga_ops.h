@@ -15,6 +15,22 @@
  *   - "prologue" = element-wise function applied to an operand as it is read, "epilogue" = applied to the result
  *     before it is written.  Activations are always prologues of the consuming op so that the tensor kept for the
  *     backward pass is the pre-activation one.
+ *
+ * Refusals (every entry point but ga_conv2d, which words its own above its descriptor; tests/test_refusals_cpu.py holds the library
+ * and tests/planref.py to these rules on a machine without a device)
+ *   - GA_E_BADARG: a NULL pointer the mode reads or writes (the ones marked optional / "or NULL" may be NULL); a size <= 0; a pitch
+ *     below the channels its tensor uses (a pitch field of 0 means the dense one); a row count that is no multiple of a replica
+ *     field in use (act_rep, dact_rep, q_rep, rep, cot_rep > 1); a replica field > 1 on a forward call where the field is
+ *     "backward, > 1"; a mode selector outside the values listed for it (where an op answers GA_E_UNSUPPORTED instead, it says so).
+ *   - GA_E_UNSUPPORTED: a channel count off the multiple an op states (C % 4, D % 4, cg % 4, dh % 16) or a pitch off the % 4 it
+ *     states; an odd H or W where the op always halves them (where a flag asks for the halving — up2 / pool2, skip_mode 1, s2d,
+ *     the planes of ga_modout — the odd size is GA_E_BADARG); a shape past what the kernel implements.
+ *   - GA_E_ALIGN: an op that states "C % 4 == 0" (D % 4, cg % 4, ld % 4) moves 16 bytes per lane, and every non-NULL tensor pointer it
+ *     reads or writes that way must be 16-byte aligned; each such op names its pointers ("16-byte aligned: ...").  No shipped plan hands
+ *     any op a pointer off 16 bytes.  The ops that move single floats take any float pointer and never answer GA_E_ALIGN:
+ *     ga_sampler_mix, ga_image_io, ga_unary, ga_gauss_blur, ga_pixelnorm, ga_rep_sum, ga_axpby, ga_split_bf16, ga_avae's PIXELNORM and
+ *     SAMPLE, and ga_dml_mean, which tests the alignment itself and falls back to single floats.
+ *   - an activation selector (act, pro_act, dact_act) outside enum ga_act is no error: the kernels treat it as GA_ACT_NONE.
  */
 #ifndef GA_OPS_H
 #define GA_OPS_H
@@ -136,6 +152,7 @@ int ga_conv2d(const ga_conv_desc* d, void* stream);
  *   backward: y = dw5_flipped(x) * act'_dact(dact_x)    with `pool2`: the 2x2 sum that is the adjoint of `up2`
  * Every row offset is formed in 64 bits (tensors past 2^32 bytes: tests/test_large_extent_gpu.py); a launch that would need more
  * than 2^31 - 1 workgroups (row blocks x tiles x 32-channel chunks) is refused with GA_E_UNSUPPORTED, for any N up to INT_MAX.
+ * C % 4 == 0.  16-byte aligned: x, w, bias, dact_x, y.  N % act_rep != 0: GA_E_BADARG.
  * ------------------------------------------------------------------------------------------------------------------ */
 typedef struct ga_dwconv5_desc {
     const float* x;      /* [N,Hs,Ws,C]; Hs = H/2 if up2 else H */
@@ -157,7 +174,9 @@ int ga_dwconv5(const ga_dwconv5_desc* d, void* stream);
  * ws (optional, ws_floats >= 2*N*C): workspace for a two-stage reduction — the pixels of a row are split over up to
  * ws_floats / (N*C) workgroups and the partial sums added in a fixed order (StyleGAN2 style gradients: 1024^2 pixels, 32
  * channels, a handful of rows).  Without it one workgroup per (row, 64 channels) walks all P pixels.
- * GA_E_UNSUPPORTED: N * ceil(C / 64) > 2^31 - 1 (the grid; the product is formed in 64 bits). */
+ * GA_E_UNSUPPORTED: N * ceil(C / 64) > 2^31 - 1 (the grid; the product is formed in 64 bits).
+ * C % 4 == 0.  16-byte aligned: a, b, out, a_src, a_w, gate, skip, scaled, and ws where the two-stage pass runs.  gate and scaled come
+ * together: one without the other is GA_E_BADARG. */
 typedef struct ga_rowchan_reduce_desc {
     const float* a; const float* b; float* out;
     int N, P, C; float scale;
@@ -175,7 +194,9 @@ int ga_rowchan_reduce(const ga_rowchan_reduce_desc* d, void* stream);
 
 /* forward : hid[n,:] = w1 m[n,:] + b1 (pre-ReLU, kept) ; gate[n,:] = sigmoid(w2 relu(hid) + b2)
  * backward: given dgate (already d/d gate), writes pro_scale[n,c] = res_scale*gate, pro_shift[n,c] = dm[n,c]/P where
- *           dm is the gradient w.r.t. the squeezed mean — the per-row affine prologue of the next backward GEMM. */
+ *           dm is the gradient w.r.t. the squeezed mean — the per-row affine prologue of the next backward GEMM.
+ * The fused form (t given) needs C % 4 == 0 and t, dout, skip, out 16-byte aligned; the unfused form takes any C and moves single
+ * floats.  Hd <= 256.  act_rep > 1 without t, with backward == 0 or with N % act_rep != 0: GA_E_BADARG. */
 typedef struct ga_se_excite_desc {
     const float* m;        /* fwd: [N,C] squeezed mean */
     const float* w1; const float* b1;   /* [Hd][C], [Hd] */
@@ -202,14 +223,17 @@ int ga_se_excite(const ga_se_excite_desc* d, void* stream);
 /* out[n,h,w,c] = skip(n,h,w,c) + res_scale * gate[n,c] * t[n,h,w,c]      (skip may be NULL with skip_mode 0: a pure row-scale)
  * skip_mode 0: skip is [N,H,W,C]; 1: skip is [N,H/2,W/2,C] read through bilinear x2, align_corners=True;
  * 2: skip is [N,2H,2W,C] sub-sampled at the even pixels (MaxPool2d(1, 2) shortcut of bottleneck_IR_SE, helpers.py:100-101)
- * (SkipUp, architecture.py:91-93; the 1x1 conv commutes with the interpolation and is applied at low resolution). */
+ * (SkipUp, architecture.py:91-93; the 1x1 conv commutes with the interpolation and is applied at low resolution).
+ * C % 4 == 0.  16-byte aligned: skip, t, gate, out.  skip NULL with skip_mode 1 or 2, odd H or W with skip_mode 1: GA_E_BADARG;
+ * skip_mode outside 0 .. 2: GA_E_UNSUPPORTED. */
 typedef struct ga_se_apply_desc {
     const float* skip; const float* t; const float* gate; float* out;
     int N, H, W, C; int skip_mode; float res_scale;
 } ga_se_apply_desc;
 int ga_se_apply(const ga_se_apply_desc* d, void* stream);
 
-/* adjoint of bilinear x2 (align_corners=True): dlow[n,h,w,c] (+)= sum over the high-res pixels it feeds */
+/* adjoint of bilinear x2 (align_corners=True): dlow[n,h,w,c] (+)= sum over the high-res pixels it feeds.
+ * C % 4 == 0.  16-byte aligned: dhigh, dlow. */
 typedef struct ga_bilinear_up2_bwd_desc {
     const float* dhigh; float* dlow; int N, h, w, C; int accumulate;
 } ga_bilinear_up2_bwd_desc;
@@ -222,7 +246,9 @@ int ga_bilinear_up2_bwd(const ga_bilinear_up2_bwd_desc* d, void* stream);
  *   z = (1-alpha) enc_mu + alpha (eps*sigma + dec_mu)
  * mu_q: [N,h,w,ldq] channels [0,NL); p: [N,h,w,ldp] = (mu_p | logsig_p) or NULL for the first group (prior N(0,1)).
  * eps is read in the reference's NCHW order [N,NL,h,w] when eps_nchw, else NHWC.
- * backward (dz given): writes dmu_q [N,h,w,ldq] and dp [N,h,w,ldp].
+ * backward (dz given): writes dmu_q [N,h,w,ldq] and dp [N,h,w,ldp] (dp with p, and only then: dp without p is GA_E_BADARG, since ldp
+ * is held to 2 NL only with p).  ldq < NL (mode 1: 2 NL), ldp < 2 NL with p, 0 < ldz < NL, in every mode: GA_E_BADARG.  mode outside
+ * 0 .. 2: GA_E_UNSUPPORTED.  act_rep > 1 with backward == 0, N % act_rep != 0 or (N / act_rep) % q_rep != 0: GA_E_BADARG.
  * ------------------------------------------------------------------------------------------------------------------ */
 typedef struct ga_sampler_desc {
     const float* mu_q; int ldq;
@@ -284,10 +310,11 @@ typedef struct ga_dml_desc {
 int ga_dml_mean(const ga_dml_desc* d, void* stream);
 
 /* 2x2/2 max pool on pre-activation maps (ReLU commutes with max), torchvision VGG 'M' entries. backward routes dy to
- * the first maximal element in (h,w) scan order. */
+ * the first maximal element in (h,w) scan order.  H, W even, C % 4 == 0.  16-byte aligned: x, y, dy, dx. */
 typedef struct ga_maxpool2_desc {
     const float* x; float* y; const float* dy; float* dx; int N, H, W, C; int backward;
-    int act_rep;      /* backward, > 1: N counts cotangent rows (dy, dx); x has N/act_rep rows, row n reads x row n / act_rep */
+    int act_rep;      /* backward, > 1: N counts cotangent rows (dy, dx); x has N/act_rep rows, row n reads x row n / act_rep.
+                         act_rep > 1 with backward == 0 or with N % act_rep != 0: GA_E_BADARG */
 } ga_maxpool2_desc;
 int ga_maxpool2(const ga_maxpool2_desc* d, void* stream);
 
@@ -297,7 +324,8 @@ int ga_maxpool2(const ga_maxpool2_desc* d, void* stream);
  * k = (kh*KW + kw)*cg + ci_local (the rows of group g read input channels g*cg .. g*cg+cg-1).
  *   y[n,ho,wo,co] = bias[co] + sum_{kh,kw,ci} act(x[n, ho*stride - pad + kh, wo*stride - pad + kw, g*cg + ci]) * w[co][...]
  *   then y *= act'(dact_x) when dact_x is given (backward use).  Taps outside the image are skipped (zero padding), so
- *   windows anchored at the output pixel (pad 0, Ho = Hi) work as for ga_conv2d. */
+ *   windows anchored at the output pixel (pad 0, Ho = Hi) work as for ga_conv2d.
+ * 16-byte aligned: x, w, bias, dact_x, y.  C % cg != 0: GA_E_BADARG. */
 typedef struct ga_gconv_desc {
     const float* x; const float* w; const float* bias; const float* dact_x; float* y;
     int N, Hi, Wi, Ho, Wo, C, cg;
@@ -325,7 +353,9 @@ int ga_unary(const ga_unary_desc* d, void* stream);
  *   forward : out[n,p,c] = act(u),  u = scale[n,c] * t[n,p,c] + add[p,c]        (scale / add may be NULL = 1 / 0)
  *   backward: dt[n,p,c]  = dout * act'(u) * scale[n,c]                          (u recomputed from t)
  * t, out, dout, dt: [N,P,C]; scale: [N,C]; add: [P,C] (noise strength * noise[p] + bias[c], row independent). C % 4 == 0.
- * With `red`: GA_E_UNSUPPORTED when N * ceil(C / 64) * segments > 2^31 - 1 (the grid). */
+ * With `red`: GA_E_UNSUPPORTED when N * ceil(C / 64) * segments > 2^31 - 1 (the grid).
+ * 16-byte aligned: t, scale, add, out, dout, dt, the planes, and ws with `red` (red itself is written one float at a time).
+ * With t_planes / dt_planes: W even, W | P, P / W even, 0 < ld_planes < C: GA_E_BADARG; ld_planes % 4 != 0: GA_E_UNSUPPORTED. */
 typedef struct ga_modout_desc {
     const float* t; const float* scale; const float* add; float* out; const float* dout; float* dt;
     int N, P, C; int act; int backward;
@@ -347,7 +377,7 @@ int ga_modout(const ga_modout_desc* d, void* stream);
 /* ToRGB's skip path (generator.py:29-46,286-288): Upsample = upfirdn2d(skip, outer(k,k)/16 * 4, up 2, pad (2, 1)), k = [1,3,3,1];
  * per axis  out[2U] = 1/4 s[U-1] + 3/4 s[U],  out[2U+1] = 3/4 s[U] + 1/4 s[U+1]  (zero beyond the border).
  *   forward : hi[n,2H,2W,C] += up(lo[n,H,W,C])          backward: lo[n,H,W,C] = up^T(hi)   (written, not accumulated)
- * C % 4 == 0. */
+ * C % 4 == 0.  16-byte aligned: lo_in, hi, hi_in, lo. */
 typedef struct ga_up2_blur_desc { const float* lo_in; float* hi; const float* hi_in; float* lo; int N, H, W, C; int backward; int _reserved; } ga_up2_blur_desc;
 int ga_up2_blur(const ga_up2_blur_desc* d, void* stream);
 
@@ -363,7 +393,9 @@ int ga_pixelnorm(const float* x, float* y, long rows, int C, void* stream);
  * replicas' cotangents in row order, each scaled by its own (1 - alpha).
  *   backward == 2: the alpha cotangent, out[r, j] = sum over D of dout[r, j, :] * (styles[r, j, :] - codes[r / rep, j, :] - avg[j, :]),
  *   a dense [R, J] table through `out` (one wavefront per (r, j), fixed summation order, no atomics).  Reads dout, styles, codes, avg
- *   (or NULL), R, J, D, rep; alpha, alpha_ld and dcodes are not read. */
+ *   (or NULL), R, J, D, rep; alpha, alpha_ld and dcodes are not read.
+ * 16-byte aligned: codes, avg, styles, out, dout, dcodes (backward == 2: codes, avg, styles, dout; `out` is written one float at a
+ * time).  alpha moves single floats.  backward outside 0 .. 2, R % rep != 0, 0 < alpha_ld < J: GA_E_BADARG. */
 typedef struct ga_latent_mix_desc {
     const float* codes; const float* avg; const float* styles; const float* alpha; float* out;
     const float* dout; float* dcodes; int R, J, D; int backward;
@@ -377,7 +409,7 @@ int ga_latent_mix(const ga_latent_mix_desc* d, void* stream);
  * pooling of the generated image [N, k*H, k*W, 4] (lanes 0..2 = RGB in [-1, 1]) and y = 0.5 * mean + 0.5, written as the
  * space-to-depth image [N, H/2, W/2, 4, ld] the ResNet stem reads (pixel (h, w) -> phase (h&1)*2 + (w&1); lanes >= 3 zero).
  *   backward: dx[n, k*h + a, k*w + b, c] = 0.5 / k^2 * (dy[n, h, w, c] + dy_nchw[n, c, h, w])  (c < 3; lane 3 zero).
- *   H, W even; ld % 4 == 0. */
+ *   H, W even; ld % 4 == 0, ld >= 4 (GA_E_BADARG below).  16-byte aligned: x, y, dy, dx (dy_nchw moves single floats). */
 typedef struct ga_pool_denorm_desc {
     const float* x; float* y; const float* dy; float* dx; int N, H, W, k, ld; int backward;
     const float* dy_nchw;     /* backward, optional: a second cotangent on the pooled image as the API returns it, [N,3,H,W]
@@ -399,7 +431,9 @@ int ga_pool_denorm(const ga_pool_denorm_desc* d, void* stream);
  * q: [N, Tq, ldq], k: [N, Tk, ldk], v: [N, Tk, ldv], out: [N, Tq, ldo]; head h = channels [h*dh, (h+1)*dh) of each (pointers may
  * address the q / k / v thirds of one in_proj output).  p: [N, heads, Tq, Tk], written by the forward, read by the backward.
  * backward: dout [N, Tq, ldo] given; WRITES dq [N, Tq, lddq], dk [N, Tk, lddk], dv [N, Tk, lddv]; ds: scratch like p.
- * Tq == 16 and dh == 128 (512 channels, 4 heads) are what the path uses; dh may be any multiple of 16 up to 128, Tq is fixed. */
+ * Tq == 16 and dh == 128 (512 channels, 4 heads) are what the path uses; dh may be any multiple of 16 up to 128, Tq is fixed
+ * (GA_E_UNSUPPORTED otherwise; dh <= 0: GA_E_BADARG).  Every pitch % 4 == 0 (GA_E_UNSUPPORTED) and >= heads * dh (GA_E_BADARG).
+ * 16-byte aligned: every pointer given. */
 typedef struct ga_attn_desc {
     const float* q; const float* k; const float* v; float* out; float* p;
     const float* dout; float* ds; float* dq; float* dk; float* dv;
@@ -412,7 +446,8 @@ int ga_attn(const ga_attn_desc* d, void* stream);
 
 /* nn.LayerNorm(C) over the channels of x = a (+ b): y = (x - mean) * rstd * gamma + beta, biased variance, eps inside the root.
  * a, b, y, dy, dx: [rows, C]; stats: [rows, 2] = (mean, rstd), written forward, read backward.
- * backward: dx (+)= d loss / d x (the same for both summands a and b). */
+ * backward: dx (+)= d loss / d x (the same for both summands a and b).
+ * C % 4 == 0.  16-byte aligned: a, b, gamma, beta, y, dy, dx (stats moves single floats). */
 typedef struct ga_layernorm_desc {
     const float* a; const float* b; const float* gamma; const float* beta; float* y; float* stats;
     const float* dy; float* dx;
@@ -422,7 +457,7 @@ int ga_layernorm(const ga_layernorm_desc* d, void* stream);
 
 /* kornia.geometry.resize(x, 2H) (bilinear, align_corners=False) followed by the row crop x[:, :, crop:-crop] of
  * TransStyleGanDefenseModel.purify (models.py:307-308: 128 -> 256 px, rows 32:-32): x [N,H,W,C] -> y [N, 2H - 2 crop, 2W, C].
- * backward: dx (+)= the exact adjoint of dy (border clamping included).  C % 4 == 0. */
+ * backward: dx (+)= the exact adjoint of dy (border clamping included).  C % 4 == 0.  16-byte aligned: x, y, dy, dx. */
 typedef struct ga_resize2_crop_desc {
     const float* x; float* y; const float* dy; float* dx; int N, H, W, C, crop; int backward; int accumulate; int _reserved;
 } ga_resize2_crop_desc;
@@ -436,7 +471,9 @@ int ga_resize2_crop(const ga_resize2_crop_desc* d, void* stream);
  *            with t1 = W1 . x + b1 and t2 = dw5(silu(t1)) + bd recomputed from x; d x follows as one 1x1 ga_conv2d of dt1.
  * Contractions are the split-bf16 products of ga_conv2d (w*_hi / w*_lo from ga_split_bf16), the depthwise part is fp32.
  *   w1 [Hd][C];  wd [25][Hd] (tap-major, forward order), wd_bwd the flipped taps;  w2: forward [C][Hd], backward W2^T [Hd][C].
- * Shapes: ga_dec_cell_supported() (C 128 or 256, H and W powers of two, whole images per 256- / 128-pixel workgroup). */
+ * Shapes: ga_dec_cell_supported() (C 128 or 256, H and W powers of two, whole images per 256- / 128-pixel workgroup); any other
+ * shape, a size <= 0 included, is GA_E_UNSUPPORTED.  b2 is read forward only, wd_bwd backward only.  16-byte aligned: x, w1_hi, w1_lo,
+ * wd, wd_bwd, bd, w2_hi, w2_lo, dout, pro_scale, pro_shift, y. */
 typedef struct ga_dec_cell_desc {
     const float* x;
     const void* w1_hi; const void* w1_lo; const float* b1;
@@ -462,7 +499,9 @@ int ga_dec_cell_supported(int N, int H, int W, int C, int Hd);   /* 1 when ga_de
  *            w2 = W2^T [Hd][C] as there, w1t = W1^T [C][Hd] (the backward weight of the expand conv), addends optional;
  *            each addend is [N,H,W,C], 16-byte aligned, and MAY ALIAS y (every element is read and written by the same thread:
  *            in-place accumulation into an already written gradient).
- * Cin == Cout in {32, 64}, Hd % 32 == 0, H % 8 == 0, W % 16 == 0 (ga_dec_cell_halo_supported); up must be 0. */
+ * Cin == Cout in {32, 64}, Hd % 32 == 0, H % 8 == 0, W % 16 == 0 (ga_dec_cell_halo_supported); up must be 0; anything else, a
+ * size <= 0 included, is GA_E_UNSUPPORTED.  b2 is read forward only; wd_bwd, w1t_hi, w1t_lo backward only.  16-byte aligned: x, y,
+ * w1_hi, w1_lo, w2_hi, w2_lo, wd, bd and, backward, dout, pro_scale, pro_shift, wd_bwd, w1t_hi, w1t_lo, addend, addend2. */
 typedef struct ga_dec_cell_halo_desc {
     const float* x;
     const void* w1_hi; const void* w1_lo; const float* b1;
@@ -492,6 +531,8 @@ int ga_dec_cell_halo_supported(int N, int H, int W, int C, int Hd);
  *   (act_rep accepted, no effect).  Every cotangent row keeps the summation order of a one-cotangent launch: a launch with
  *   act_rep = K gives the bits of K launches with act_rep = 1 on the cotangent slices.  act_rep > 1 with backward == 0 or with
  *   N % act_rep != 0: GA_E_BADARG.
+ * ADAIN and AVGPOOL need C % 4 == 0; 16-byte aligned: ADAIN x, b, c, dy, y; AVGPOOL x, y, dy.  AVGPOOL: k | H and k | W, else
+ * GA_E_BADARG.  mode outside 0 .. 3: GA_E_UNSUPPORTED.
  * ------------------------------------------------------------------------------------------------------------------ */
 enum { GA_AVAE_ADAIN = 0, GA_AVAE_AVGPOOL = 1, GA_AVAE_PIXELNORM = 2, GA_AVAE_SAMPLE = 3 };
 typedef struct ga_avae_desc {
@@ -515,7 +556,7 @@ int ga_microbench_mfma_bf16_shape(float* out, int blocks, int iters, int shape, 
 
 /* nn.PReLU(C) as a stand-alone pass (the input layer of the e4e encoder, encoder.py:72-74, whose output feeds both an
  * affine prologue and a shortcut): forward y = x > 0 ? x : slope[c] * x; backward dx = dy * (x > 0 ? 1 : slope[c]).
- * x: [rows][C], C % 4 == 0. */
+ * x: [rows][C], C % 4 == 0.  16-byte aligned: x, slope, y, dy, dx. */
 typedef struct ga_prelu_desc {
     const float* x; const float* slope; float* y; const float* dy; float* dx; long rows; int C; int backward;
 } ga_prelu_desc;
@@ -524,7 +565,7 @@ int ga_prelu(const ga_prelu_desc* d, void* stream);
 /* 3x3 / stride 2 / pad 1 max pool (torchvision ResNet stem, resnet.py `self.maxpool`), on pre-activation maps (ReLU
  * commutes with max).  x: [N,H,W,C], y: [N,H/2,W/2,C] (H, W even).  backward: dx[p] = sum of dy over the windows whose
  * first maximal element in scan order is p (aten::max_pool2d_with_indices keeps the first), gathered per input pixel:
- * deterministic, no atomics. */
+ * deterministic, no atomics.  C % 4 == 0.  16-byte aligned: x, y, dy, dx. */
 typedef struct ga_maxpool3s2_desc {
     const float* x; float* y; const float* dy; float* dx; int N, H, W, C; int backward;
     int act_rep;      /* backward, > 1: N counts cotangent rows (dy, dx); x has N/act_rep rows, cotangent row n re-scans x row
@@ -535,7 +576,7 @@ int ga_maxpool3s2(const ga_maxpool3s2_desc* d, void* stream);
 
 /* Global average pool with an activation prologue (torchvision ResNet `avgpool` after the last block's ReLU):
  * forward  y[n,c] = mean_p act(x[n,p,c]);  backward dx[n,p,c] = dy[n,c] / P * act'(x[n,p,c]).  x: [N,P,C], C % 4 == 0.
- * GA_E_UNSUPPORTED: N * ceil(C / 64) > 2^31 - 1 (the grid). */
+ * GA_E_UNSUPPORTED: N * ceil(C / 64) > 2^31 - 1 (the grid).  16-byte aligned: x, y, dy, dx. */
 typedef struct ga_avgpool_act_desc {
     const float* x; float* y; const float* dy; float* dx; int N, P, C; int act; int backward;
     int act_rep;      /* backward, > 1: N counts cotangent rows (dy, dx); x has N/act_rep rows, cotangent row n reads x row
@@ -596,7 +637,9 @@ int ga_rep_sum(const float* x, float* y, long rows, long inner, int rep, int acc
  * kernel (weights: folding.subpixel_weights).  This op interleaves their dense results s[a][b] = [N, H/2, W/2, C] into
  * y = [N, H, W, C] and applies the conv epilogue on the way:
  *   y[n, 2i+a, 2j+b, c] = s[a][b][n, i, j, c] * act'(dact_x*dact_scale + dact_shift)*dact_scale + addend + addend2
- * A NULL s[a][b] is a zero plane (a 1x1 stride-2 conv only feeds parity (0, 0)).  addend may alias y. */
+ * A NULL s[a][b] is a zero plane (a 1x1 stride-2 conv only feeds parity (0, 0)).  addend may alias y.
+ * 16-byte aligned: every pointer given.  0 < lds < C: GA_E_BADARG; lds % 4 != 0: GA_E_UNSUPPORTED (the planes are read 16 bytes per
+ * lane).  N % dact_rep != 0 with dact_x given: GA_E_BADARG, as ga_gconv.  dact_scale and dact_shift come together unless dact_prelu. */
 typedef struct ga_interleave2_desc {
     const float* s[2][2];
     float* y;
@@ -813,6 +856,11 @@ const char* ga_last_hip_error(void);
 /* (ga_nes_perturb and ga_nes_grad likewise: entry points of their own with scalar arguments, no descriptor, ga_op untouched, and a
  * library without them is refused by name when the binding looks them up: the version stays.) */
 /* (ga_square_linf and ga_square_l2 likewise.) */
+/* (The refusals spelled out under "Refusals" and per op — ga_sampler_mix ldz and dp without p, ga_modout ld_planes, ga_interleave2 lds
+ * and dact_rep, ga_latent_mix backward outside 0 .. 2, ga_attn dh <= 0, ga_rowchan_reduce gate without scaled, GA_E_ALIGN in
+ * ga_maxpool2, ga_maxpool3s2, ga_prelu, ga_modout, ga_up2_blur, ga_interleave2, ga_latent_mix, ga_avgpool_act, ga_pool_denorm — refuse
+ * descriptors whose behaviour was undefined before (reads or writes past a buffer, or 16-byte accesses off their boundary): no layout
+ * and no defined call changes, so the version stays.) */
 #define GA_ABI_VERSION 8
 int ga_abi_version(void);
 unsigned long ga_sizeof_op(void);

@@ -71,7 +71,8 @@ def test_bad_descriptors_are_rejected_without_a_gpu():
                      (L.ModoutDesc(), L.lib.ga_modout), (L.Up2BlurDesc(), L.lib.ga_up2_blur),
                      (L.LatentMixDesc(), L.lib.ga_latent_mix), (L.PoolDenormDesc(), L.lib.ga_pool_denorm),
                      (L.AttnDesc(), L.lib.ga_attn), (L.LayernormDesc(), L.lib.ga_layernorm),
-                     (L.Resize2CropDesc(), L.lib.ga_resize2_crop), (L.DecCellDesc(), L.lib.ga_dec_cell)):
+                     (L.Resize2CropDesc(), L.lib.ga_resize2_crop), (L.DecCellDesc(), L.lib.ga_dec_cell),
+                     (L.AvaeDesc(), L.lib.ga_avae), (L.DecCellHaloDesc(), L.lib.ga_dec_cell_halo)):
         assert fn(C.byref(desc), None) == -1
     assert L.lib.ga_plan_run(None, 0, None, None) == -1
     assert L.lib.ga_pixelnorm(None, None, 4, 512, None) == -1
